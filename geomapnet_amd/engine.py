@@ -327,7 +327,7 @@ class Engine:
     #    stream's implicit synchronisation would serialise
     def step_stream(self):
         """ONE step stream per device for the whole process, created before the library's weight-gradient side stream.
-        HIP streams are multiplexed onto a small number of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) in creation order, and
+        HIP streams are multiplexed onto a small number of hardware queues (four by default) in creation order, and
         two streams that land on the same queue execute in order: round 5's "every fourth model of a process is 7-11 % slow" was a
         new torch stream per Engine walking round that ring until the step stream shared a queue with the library's side stream --
         the step lost the overlap of its weight-gradient launches, exactly the ~1.3 ms the second stream buys

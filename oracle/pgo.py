@@ -12,10 +12,10 @@ published definitions (quaternions are [w, x, y, z]):
   qconjugate(q)      q * [1, -1, -1, -1]
   qinverse(q)        qconjugate(q) / dot(q, q)
   rotate_vector(v,q) (q (0, v) q*)[1:]        -- with q* the CONJUGATE, so a non-unit q scales the result by |q|^2
-Pinned by tests/test_oracle_pinned_to_reference.py: the reference's own PoseGraph / PoseGraphFC classes are executed
-from /root/reference with these three functions bound as `txq` and must agree with `optimize_window` below; golden
-vectors (tests/golden/pgo.npz) come from that execution, including the reference's own fixture `pgo_test_poses1`
-(:1146-1169).
+Pinned by tests/test_oracle_pinned_to_reference.py: the reference's own PoseGraph / PoseGraphFC classes, executed
+with these three functions bound as `txq` (tests/golden/make_golden.py), must agree with `optimize_window` below; golden
+vectors (tests/golden/pgo.npz, tests/golden/reference_pins.npz) come from that execution, including the reference's own
+fixture `pgo_test_poses1` (:1146-1169).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this package.
 """

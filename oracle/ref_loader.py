@@ -2,8 +2,8 @@
 
 Only usable where the reference tree is mounted (this build container); the GPU box has no
 /root/reference, so nothing that runs there may call this.  Used by
-tests/test_oracle_pinned_to_reference.py and tests/golden/make_golden.py to pin the oracle
-restatement to the reference implementation itself.
+tests/golden/make_golden.py to record the reference's outputs that pin the oracle restatement
+(tests/test_oracle_golden.py, tests/test_oracle_pinned_to_reference.py).
 
 What is executed unmodified:
   * models/posenet.py              (PoseNet, MapNet, filter_hook)

@@ -13,6 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, os.path.dirname(HERE))  # tests/checks.py: the seeded pose-graph windows
 warnings.filterwarnings("ignore")
 
 import oracle  # noqa: E402
@@ -141,8 +142,150 @@ def make_pgo(ns):
     np.savez_compressed(os.path.join(HERE, "pgo.npz"), **out)
 
 
+def tensor_digest(t):
+    """sha256 over dtype, shape and bytes: equal digests <=> torch.equal on tensors of one dtype"""
+    import hashlib
+    a = t.detach().contiguous().cpu().numpy()
+    return hashlib.sha256(("%s%s" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+def one_thread():
+    """torch's CPU convolutions sum in an order that depends on the thread count: the network passes whose outputs are
+    stored for tests/test_oracle_pinned_to_reference.py run on one thread, there and here"""
+    import contextlib
+
+    @contextlib.contextmanager
+    def ctx():
+        n = torch.get_num_threads()
+        torch.set_num_threads(1)
+        try:
+            yield
+        finally:
+            torch.set_num_threads(n)
+    return ctx()
+
+
+PIN_FULL_NUMEL = 8192   # parameter gradients up to this size are stored whole, larger ones as a fixed sample + their norm
+PIN_SAMPLE = 2048
+
+
+def make_reference_pins(ns):
+    """what tests/test_oracle_pinned_to_reference.py checks the oracle against: the reference's own outputs (criteria with
+    their gradients, pose chains, PoseNet / MapNet modules, the NaN filter hook, the numpy metric helpers, batch construction,
+    the pose-graph optimisation) on the inputs those tests build"""
+    import checks
+    from oracle import pgo as opgo
+    out = {}
+    C = ns.criterion
+    for n in (1, 5, 33):  # test_criteria_fp64
+        gen = torch.Generator().manual_seed(n)
+        targ = _poses(gen, n, 3).double()
+        pred = targ + 0.4 * torch.randn(n, 3, 6, generator=gen).double()
+        pairs = [(C.PoseNetCriterion(sax=0.2, saq=-3, learn_beta=True), pred[:, 0], targ[:, 0]),
+                 (C.MapNetCriterion(sax=0.2, saq=-3, srx=0.1, srq=-3, learn_beta=True, learn_gamma=True), pred, targ)]
+        _, to = oracle.make_batch("mapnet++", n, 2, 2, seed=n)
+        po = torch.cat((to[:, :3], _poses(gen, n, 3)), 1).double() + 0.1 * torch.randn(n, 6, 6, generator=gen).double()
+        pairs.append((ns.MapNetOnlineCriterionPy3(saq=-3, srq=-3, learn_beta=True, learn_gamma=True), po, to.double()))
+        _, tg = oracle.make_batch("mapnet++", n, 2, 2, seed=n, gps_mode=True)
+        pairs.append((ns.MapNetOnlineCriterionPy3(saq=-3, srq=-3, learn_beta=True, learn_gamma=True, gps_mode=True),
+                      tg.double() + 0.1 * torch.randn(n, 6, 6, generator=gen).double(), tg.double()))
+        for i, (rc, p, t) in enumerate(pairs):
+            rc = rc.double()
+            p1 = p.clone().requires_grad_(True)
+            loss = rc(p1, t)
+            loss.backward()
+            k = "crit/n%d/%d/" % (n, i)
+            out[k + "pred"], out[k + "targ"] = p.numpy(), t.numpy()
+            out[k + "loss"], out[k + "dpred"] = np.float64(loss.item()), p1.grad.numpy()
+            sg = [getattr(rc, nm).grad if hasattr(rc, nm) else None for nm in ("sax", "saq", "srx", "srq")]
+            out[k + "dparam_present"] = np.array([g is not None for g in sg])
+            out[k + "dparam"] = np.array([g.item() if g is not None else np.nan for g in sg])
+    P = ns.pose_utils  # test_pose_chain_fp32_and_identities
+    gen = torch.Generator().manual_seed(3)
+    poses = _poses(gen, 9, 4)
+    out["chain/poses"] = poses.numpy()
+    out["chain/calc_vos"], out["chain/calc_vos_simple"] = P.calc_vos(poses).numpy(), P.calc_vos_simple(poses).numpy()
+    p = poses[0, :1]
+    out["chain/vo_logq_self"] = P.calc_vo_logq(p, p).numpy()
+    p7 = torch.cat((p[:, :3], P.qexp_t(p[:, 3:])), 1)
+    out["chain/compose_inverse"] = P.compose_pose_quaternion(p7, P.invert_pose_quaternion(p7)).numpy()
+    torch.manual_seed(11)  # test_posenet_module_equivalence
+    a = ns.posenet.MapNet(ns.posenet.PoseNet(oracle.resnet34(), droprate=0.0, pretrained=False))
+    sd = a.state_dict()
+    out["module/keys"] = np.array(list(sd.keys()))
+    out["module/digests"] = np.array([tensor_digest(v) for v in sd.values()])
+    x, _ = oracle.make_batch("mapnet", 2, 32, 43)
+    out["module/x"] = x.numpy()
+    with one_thread():
+        out["module/out"] = a(x).detach().numpy()
+    torch.manual_seed(5)  # test_filter_nans_hook_equivalence
+    a = ns.posenet.PoseNet(oracle.resnet34(), droprate=0.0, pretrained=False, filter_nans=True)
+    x, _ = oracle.make_batch("posenet", 3, 32, 43)
+    cot = torch.ones(3, 6)
+    cot[1, 4] = float("nan")
+    a.zero_grad()
+    with one_thread():
+        (a(x) * cot).sum().backward()
+    out["nan_filter/x"], out["nan_filter/cot"] = x.numpy(), cot.numpy()
+    names, rng = [], np.random.RandomState(20260101)
+    for i, (k, q) in enumerate(a.named_parameters()):
+        g = q.grad.detach().reshape(-1).numpy()
+        names.append(k)
+        if g.size <= PIN_FULL_NUMEL:
+            out["nan_filter/%d/val" % i] = g
+        else:
+            idx = np.sort(rng.choice(g.size, PIN_SAMPLE, replace=False)).astype(np.int32)
+            out["nan_filter/%d/idx" % i], out["nan_filter/%d/val" % i] = idx, g[idx]
+        out["nan_filter/%d/norm" % i] = np.float64(np.linalg.norm(g.astype(np.float64)))
+        out["nan_filter/%d/nans" % i] = np.int64(np.isnan(g).sum())
+    out["nan_filter/names"] = np.array(names)
+    PN = ns.pose_utils_np  # test_numpy_metric_helpers_are_the_reference_ones
+    rng = np.random.RandomState(3)
+    vw = []
+    for _ in range(50):
+        v, w = rng.randn(3) * rng.uniform(0, 1.5), rng.randn(3) * rng.uniform(0, 1.5)
+        vw.append((v, w))
+    out["np_metric/v"], out["np_metric/w"] = np.array([v for v, _ in vw]), np.array([w for _, w in vw])
+    out["np_metric/qexp_v"] = np.array([PN.qexp(v) for v, _ in vw])
+    out["np_metric/angular_error"] = np.array([PN.quaternion_angular_error(PN.qexp(v), PN.qexp(w)) for v, w in vw])
+    out["np_metric/qlog_qexp_v"] = np.array([PN.qlog(PN.qexp(v)) for v, _ in vw])
+    out["np_metric/qexp_zero"] = PN.qexp(np.zeros(3))
+    gen = torch.Generator().manual_seed(99)  # test_batch_construction_helpers_are_the_reference_ones
+    poses = _poses(gen, 4, 3)
+    out["vos_safe/poses"], out["vos_safe/want"] = poses.numpy(), P.calc_vos_safe(poses).numpy()
+    PG = ns.pgo  # test_pose_graph_optimisation_is_the_reference_one
+    L = [np.eye(3) * 0.7, np.eye(4) * 1.3, np.eye(3) * 0.9, np.eye(4) * 1.1]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for fc in (False, True):
+            pred, vos, gt = checks.pgo_windows(3, 6, fc, seed=5)
+            k = "pgo/fc%d/" % fc
+            out[k + "pred"], out[k + "vos"], out[k + "gt"] = pred, vos, gt
+            jac, res, opt = [], [], []
+            for w in range(3):
+                g = (PG.PoseGraphFC if fc else PG.PoseGraph)()
+                g.N, g.z = 6, pred[w].copy().reshape(-1, 1)
+                jac.append(g.jacobian(*L))
+                res.append(g.residuals(gt[w].copy(), vos[w].copy(), *L)[:, 0])
+                opt.append((PG.PoseGraphFC if fc else PG.PoseGraph)().optimize(pred[w], vos[w], sax=0.5, saq=2.0, srx=0.25, srq=4.0))
+            out[k + "jacobian"], out[k + "residuals"], out[k + "opt"] = np.stack(jac), np.stack(res), np.stack(opt)
+        fposes, fvos = PG.pgo_test_poses1()
+        out["pgo/fixture/poses"], out["pgo/fixture/vos"] = fposes, fvos
+        out["pgo/fixture/opt"] = PG.PoseGraph().optimize(fposes, fvos)
+        out["pgo/from_targets/opt"] = PG.optimize_poses(pred[0], target_poses=gt[0])
+    gen = torch.Generator().manual_seed(17)  # test_fully_connected_vo_targets_are_the_reference_ones
+    poses = _poses(gen, 3, 5)
+    out["vos_fc/poses"], out["vos_fc/want"] = poses.numpy(), P.calc_vos_safe_fc(poses).numpy()
+    assert not any(v.dtype == object for v in out.values())
+    np.savez_compressed(os.path.join(HERE, "reference_pins.npz"), **out)
+
+
 def main():
     ns = ref_loader.load()
+    if sys.argv[1:] == ["reference_pins"]:
+        make_reference_pins(ns)
+        print("wrote reference_pins.npz")
+        return
     if sys.argv[1:] == ["pgo"]:
         make_pgo(ns)
         print("wrote pgo.npz")
@@ -158,6 +301,7 @@ def main():
     make_eval_metric(ns)
     make_batch_construction(ns)
     make_pgo(ns)
+    make_reference_pins(ns)
     C = ns.criterion
     gen = torch.Generator().manual_seed(1234)
     cases = {}

@@ -6,17 +6,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = ["--emu", "--steps", "1", "--warmup", "0", "--windows", "1", "--height", "32", "--width", "40", "--dtype", "fp32"]
 
 
-def _run(extra):
+def _run(extra, tiny=TINY):
     env = dict(os.environ, MAPNET_EMU_THREADS="4")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + TINY, env=env, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + tiny, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -41,6 +42,28 @@ def test_bench_single_rank_reports_parity_and_cpu_baseline():
     assert p["dtype"] == "fp32" and p["loss_rel"] <= 1e-4 and p["pose_abs_max"] <= 1e-3, p
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["cpu"]
+
+
+@pytest.mark.slow
+def test_bench_dumps_what_the_last_timed_step_returned(tmp_path):
+    """the last timed step starts from the seeded initial state, so it returns what the first warm-up step returned"""
+    d = _run(["--gpus", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], TINY + ["--warmup", "1", "--steps", "2"])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["config"]["loss_last"] - d["config"]["loss_first"]) <= 1e-4 * max(1.0, abs(d["config"]["loss_first"]))
+    loss, poses = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "poses.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and poses.dtype == np.float32 and poses.shape == (1, 3, 6)
+    assert np.isfinite(poses).all() and abs(float(loss[0]) - d["config"]["loss_last"]) <= 5e-5 * max(1.0, abs(float(loss[0])))
+    assert sorted(d["dump_outputs"]["arrays"]) == ["loss", "poses"]
+
+
+def test_bench_steps_are_the_timed_steps_in_all():
+    """--steps K times K steps in all, split into at most --repeats regions of nearly equal length"""
+    sys.path.insert(0, ROOT)
+    import bench
+    for steps in (1, 2, 5, 7, 50, 101):
+        for repeats in (1, 3, 5, 200):
+            sizes = bench.region_sizes(steps, repeats)
+            assert sum(sizes) == steps and len(sizes) == min(steps, repeats) and max(sizes) - min(sizes) <= 1
 
 
 def test_bench_rejects_a_launcher_rank_count_mismatch():
