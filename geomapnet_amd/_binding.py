@@ -58,6 +58,8 @@ _PROTOS = {
     "mn_set_dropout": (c_i, [c_void, c_f, C.c_uint64]),
     "mn_set_dropout_calls": (c_i, [c_void, C.c_uint32]),
     "mn_set_input_u8": (c_i, [c_void, c_i, C.POINTER(c_f), C.POINTER(c_f)]),
+    "mn_set_color_jitter": (c_i, [c_void, c_f, c_f, c_f, c_f, C.c_uint64]),
+    "mn_set_color_jitter_calls": (c_i, [c_void, C.c_uint32]),
     "mn_forward": (c_i, [c_void, c_void, c_void, c_i, c_void]),
     "mn_loss": (c_i, [c_void, c_void, c_void, c_void, c_void]),
     "mn_train_step": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void]),
@@ -104,6 +106,8 @@ _PROTOS = {
     "mn_op_maxpool_fwd": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_maxpool_bwd": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_occupy": (c_i, [c_i, c_i, c_f, c_void, c_void, c_i64, c_i, c_void]),
+    "mn_op_color_jitter": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, C.POINTER(c_f), C.c_uint64, C.c_uint32,
+                                 C.POINTER(c_f), C.POINTER(c_f), c_void]),
 }
 
 SYMBOLS = tuple(_PROTOS)

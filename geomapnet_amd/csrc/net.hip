@@ -15,6 +15,7 @@
 #include "elementwise.h"
 #include "elementwise_h2.h"
 #include "head.h"
+#include "jitter.h"
 #include "dense.h"
 #include "igemm.h"
 #include "dgrad.h"
@@ -216,6 +217,13 @@ struct PlanBase {
   bool drop_this_step = false;  // the forward pass of the step being built applied a mask (the backward pass must, too)
   bool input_u8 = false;  // images are uint8 NHWC, normalised on the device (mn_set_input_u8)
   InputNorm input_norm{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}};
+  InputNorm jitter_norm{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}};  // the same Normalize on x in [0, 1]: scale 1/std, shift -mean/std
+  // ColorJitter on uint8 input (mn_set_color_jitter): ranges (brightness, contrast, saturation, hue), Philox key, jittered passes
+  // so far; all ranges 0 = off, and the forward pass launches exactly what it launches without jitter
+  float jit_range[4] = {0.f, 0.f, 0.f, 0.f};
+  unsigned long long jit_seed = 0;
+  unsigned jit_calls = 0;
+  bool jitter_on() const { return jit_range[0] > 0.f || jit_range[1] > 0.f || jit_range[2] > 0.f || jit_range[3] > 0.f; }
   virtual int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) = 0;
   virtual int forward_loss(const void* images, const float* targets, float* loss_out, float* poses_out,
                            hipStream_t s) = 0;
@@ -346,6 +354,7 @@ struct Plan : PlanBase {
   std::vector<Block> blocks;
   int Hl, Wl;  // last feature map
   float *pooled, *feat, *poses, *dposes, *dz, *dpooled, *fcT, *loss_dev, *dropmask;
+  float *jit_draws, *jit_partials, *jit_mean;  // ColorJitter: [B][8] draws, [B][kJitterChunks] gray sums, [B] mean gray
   // BatchNorm sums are accumulated with fp64 atomics straight from the producing kernels (conv epilogue, backward
   // reduction) into ACC_ROWS rows per unit (row = producer block % ACC_ROWS, to spread same-address contention);
   // the consuming apply kernels add the rows in their prologue.  No separate partial-reduction launches.
@@ -486,6 +495,9 @@ struct Plan : PlanBase {
     step_dev = (long long*)A(256);
     bc_dev = (float*)A(256);
     overflow_dev = (long long*)A(256);
+    jit_draws = (float*)A((size_t)B * 8 * 4);  // (last: the buffers above keep their offsets)
+    jit_partials = (float*)A((size_t)B * kJitterChunks * 4);
+    jit_mean = (float*)A((size_t)B * 4);
     return b.cur;
   }
 
@@ -796,10 +808,20 @@ struct Plan : PlanBase {
                        np, u.cp.cout, relu);
   }
 
+  // ColorJitter + ToTensor + Normalize (jitter.h); every jittered pass advances jit_calls by one
+  void launch_jitter_input(const unsigned char* images, half* x16, hipStream_t s) {
+    launch_u8_jitter<T>(images, xpad, B, H, W, Hp, Wp, jitter_norm, x16, jitter_params(jit_range, jit_seed, jit_calls), jit_draws,
+                        jit_partials, jit_mean, s);
+    jit_calls += 1;
+  }
+
   int forward(const void* images, float* poses_out, int training, hipStream_t s) override {
     return forward_impl(images, poses_out, training, false, s);
   }
   int forward_impl(const void* images, float* poses_out, int training, bool zero_grads, hipStream_t s) {
+    if (jitter_on() && !input_u8)
+      return fail("forward: ColorJitter (mn_set_color_jitter) needs uint8 input (mn_set_input_u8): fp32 frames arrive already "
+                  "normalised, and ColorJitter must come before Normalize");
     // work the stem and layer1 do not depend on goes to the side stream: the repack of the later layers'
     // weights and optim.learner.zero_grad(); joined before layer2
     const bool dirty = weights_dirty;
@@ -812,7 +834,9 @@ struct Plan : PlanBase {
     }
     // (fp16x2m: the stem's fp16 backward kernels read an fp16 image of the input -- written by the same launch)
     half* const x16 = stem_bwd_f16() && training ? xpad16 : (half*)nullptr;
-    if (input_u8)
+    if (input_u8 && jitter_on())
+      launch_jitter_input((const unsigned char*)images, x16, s);
+    else if (input_u8)
       hipLaunchKernelGGL((u8nhwc_to_padded_nhwc4_kernel<T>), dim3(ew_grid((long)B * Hp * Wp)), dim3(256), 0, s,
                          (const unsigned char*)images, xpad, B, H, W, Hp, Wp, input_norm, x16);
     else
@@ -1255,6 +1279,7 @@ struct Plan : PlanBase {
     if (n == "dz") return give(dz, (long)B * cfg.feat_dim, MN_F32);
     if (n == "dpooled") return give(dpooled, (long)B * 512, MN_F32);
     if (n == "dropmask") return give(dropmask, (long)B * cfg.feat_dim, MN_F32);
+    if (n == "jitter") return give(jit_draws, (long)B * 8, MN_F32);
     if (n.size() > 2 && n[0] == 'b') {  // "b<block>.<tensor>", blocks numbered 0..15 in network order
       const size_t dot = n.find('.');
       if (dot != std::string::npos) {
@@ -1499,8 +1524,27 @@ extern "C" int mn_set_input_u8(mn_handle* h, int enable, const float* mean, cons
       if (!(std[c] > 0.f)) return fail("mn_set_input_u8: std must be positive");
       P.input_norm.scale[c] = 1.f / (255.f * std[c]);
       P.input_norm.shift[c] = -mean[c] / std[c];
+      P.jitter_norm.scale[c] = 1.f / std[c];
+      P.jitter_norm.shift[c] = -mean[c] / std[c];
     }
   P.input_u8 = enable != 0;
+  return 0;
+}
+extern "C" int mn_set_color_jitter(mn_handle* h, float brightness, float contrast, float saturation, float hue, uint64_t seed) {
+  MN_H(h);
+  const float v[4] = {brightness, contrast, saturation, hue};
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(v[k]) || !(v[k] >= 0.f))
+      return fail("mn_set_color_jitter: brightness, contrast, saturation and hue must be finite and >= 0");
+  if (!(hue <= 0.5f)) return fail("mn_set_color_jitter: 0 <= hue <= 0.5 required");
+  for (int k = 0; k < 4; ++k) P.jit_range[k] = v[k];
+  P.jit_seed = seed;
+  P.jit_calls = 0;
+  return 0;
+}
+extern "C" int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls) {
+  MN_H(h);
+  P.jit_calls = calls;
   return 0;
 }
 extern "C" int mn_forward(mn_handle* h, const void* images, float* poses_out, int training, void* stream) {

@@ -7,6 +7,7 @@
 #include "criterion.h"
 #include "elementwise.h"
 #include "head.h"
+#include "jitter.h"
 #include "dense.h"
 #include "igemm.h"
 #include "dgrad.h"
@@ -419,4 +420,21 @@ extern "C" int mn_op_occupy(int workgroups, int threads, float microseconds, con
   if (lds_kb != 0 && lds_kb != 32 && lds_kb != 64) return fail("mn_op_occupy: lds_kb must be 0, 32 or 64");
   launch_occupy(workgroups, threads, microseconds, src, dst, (long)bytes, lds_kb, (hipStream_t)stream);
   return check_launch("occupy");
+}
+
+extern "C" int mn_op_color_jitter(const unsigned char* in, float* out, float* draws, float* work, int B, int H, int W,
+                                  const float* ranges, uint64_t seed, uint32_t call, const float* mean, const float* std,
+                                  void* stream) {
+  begin_call();
+  if (B < 1 || H < 1 || W < 1 || !in || !out || !draws || !work || !ranges || !mean || !std)
+    return fail("mn_op_color_jitter: B, H, W >= 1 and every pointer required");
+  InputNorm nm;
+  for (int c = 0; c < 3; ++c) {
+    if (!(std[c] > 0.f)) return fail("mn_op_color_jitter: std must be positive");
+    nm.scale[c] = 1.f / std[c];
+    nm.shift[c] = -mean[c] / std[c];
+  }
+  launch_u8_jitter<float>(in, out, B, H, W, H + 6, W + 6, nm, nullptr, jitter_params(ranges, seed, call), draws, work,
+                          work + (long)B * kJitterChunks, (hipStream_t)stream);
+  return check_launch("color_jitter");
 }

@@ -181,7 +181,9 @@ def _standin_launch(engine, lib, bucket, cfg):
 def _staged_step(engine, plan, images, targets, lib, h, s):
     import ctypes as C
     poses = plan["poses"]
+    engine._jitter_pass(plan)
     lib.check(lib.train_forward_loss(h, ptr(images), ptr(targets), ptr(plan["loss"]), ptr(poses), s))
+    engine._jitter_passed(plan)
     grads = engine.grads()
     works = []
     multi = world_size() > 1 or (dist.is_available() and dist.is_initialized())

@@ -5,6 +5,7 @@ BatchNorm buffers, per-plan work arena) and as the source of the current HIP str
 arithmetic happens in libmapnet_hip.so.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -104,6 +105,10 @@ class Engine:
         self.eps_mode = 0
         self.input_u8 = None  # (mean[3], std[3]) when images arrive as uint8 NHWC and are normalised on the device
         self.dropout = (0.0, 0)  # (p, Philox seed) of the device dropout on the feature vector (mn_set_dropout); p = 0: identity
+        # (brightness, contrast, saturation, hue, Philox seed) of the device ColorJitter on uint8 input (mn_set_color_jitter); ranges
+        # all 0: off.  jitter_calls: jittered forward passes of this model so far, whichever plan ran them (the Philox counter)
+        self.color_jitter = (0.0, 0.0, 0.0, 0.0, 0)
+        self.jitter_calls = 0
 
     # -- arenas ---------------------------------------------------------------------------------
     @property
@@ -215,8 +220,30 @@ class Engine:
                 # counter, and _own_step returns early for the owner -- the sequence would replay its first masks)
                 self._read_step()
                 self.lib.check(self.lib.set_dropout_calls(p["handle"], self.step_count & 0xffffffff))
+        if p.get("color_jitter", (0.0, 0.0, 0.0, 0.0, 0)) != self.color_jitter:
+            b, c, s, h, seed = self.color_jitter
+            self.lib.check(self.lib.set_color_jitter(p["handle"], C.c_float(b), C.c_float(c), C.c_float(s), C.c_float(h),
+                                                     C.c_uint64(seed)))
+            p["color_jitter"] = self.color_jitter
+            p["jitter_calls"] = 0  # (mn_set_color_jitter restarts the plan's count; _jitter_pass continues the model's)
         self._own_step(p)
         return p
+
+    def jitter_active(self):
+        return self.input_u8 is not None and any(v > 0.0 for v in self.color_jitter[:4])
+
+    def _jitter_pass(self, p):
+        """before a forward pass of plan `p`: the plan's Philox pass count := the model's (a plan that did not run the model's
+        last jittered pass -- the last partial batch, a validation batch, a resumed model -- would otherwise replay draws)"""
+        if self.jitter_active() and p.get("jitter_calls") != self.jitter_calls:
+            self.lib.check(self.lib.set_color_jitter_calls(p["handle"], self.jitter_calls & 0xffffffff))
+            p["jitter_calls"] = self.jitter_calls
+
+    def _jitter_passed(self, p):
+        """after a forward pass of plan `p` was enqueued: the library advanced the plan's count by one"""
+        if self.jitter_active():
+            self.jitter_calls += 1
+            p["jitter_calls"] = self.jitter_calls
 
     def params_touched(self):
         self.version += 1
@@ -288,6 +315,29 @@ class Engine:
         out.copy_(plan["work"][off:off + 4 * n.value].view(torch.float32))
         return out.view(plan["images"], self.feat_dim)
 
+    def set_color_jitter(self, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, seed=0):
+        """torchvision's ColorJitter on uint8 input, on the device, before Normalize (include/mapnet_hip.h mn_set_color_jitter):
+        every forward pass of a uint8 plan draws fresh factors and op order per image.  All ranges 0 disables it.  The model's
+        pass count (jitter_calls) is kept: it continues across plans and across a change of settings."""
+        vals = [float(v) for v in (brightness, contrast, saturation, hue)]
+        if not all(math.isfinite(v) and v >= 0.0 for v in vals) or vals[3] > 0.5:
+            raise MapNetHipError("set_color_jitter: ranges must be finite and >= 0, hue <= 0.5")
+        self.color_jitter = tuple(vals) + (int(seed) & 0xffffffffffffffff,)
+
+    def set_color_jitter_calls(self, calls):
+        """the model's count of jittered passes: the next pass draws what pass `calls` of this seed draws (checkpoint resume)"""
+        self.jitter_calls = int(calls)
+
+    def color_jitter_draws(self, plan):
+        """[images, 8] draws of the last jittered pass of `plan`: brightness, contrast, saturation and hue factors, then the four op
+        ids (0 brightness, 1 contrast, 2 saturation, 3 hue) in the order they were applied (tests, tools)"""
+        ptr_, n, dt = C.c_void_p(), C.c_int64(), C.c_int32()
+        self.lib.check(self.lib.debug_tensor(plan["handle"], b"jitter", C.byref(ptr_), C.byref(n), C.byref(dt)))
+        if self.params.is_cuda:
+            torch.cuda.synchronize(self.device)
+        off = ptr_.value - plan["work"].data_ptr()
+        return plan["work"][off:off + 4 * n.value].view(torch.float32).clone().cpu().view(plan["images"], 8)
+
     def set_input_u8(self, mean=None, std=None):
         """images become uint8 [.., H, W, 3]; (x/255 - mean)/std runs on the device.  mean=None: back to fp32 NCHW."""
         self.input_u8 = None if mean is None else (tuple(float(v) for v in mean), tuple(float(v) for v in std))
@@ -308,7 +358,9 @@ class Engine:
         H, W = self.image_dims(images)
         p = self.plan(MODE_POSENET, B, 1, H, W)
         out = torch.empty(B, 6, dtype=torch.float32, device=self.device)
+        self._jitter_pass(p)
         self.lib.check(self.lib.forward(p["handle"], ptr(images), ptr(out), int(bool(training)), _stream(images)))
+        self._jitter_passed(p)
         return out
 
     def configure_step(self, p, lr, weight_decay, betas, eps, max_grad_norm, learn_beta, learn_gamma, method=(0, 0)):
@@ -348,8 +400,10 @@ class Engine:
                 p["loss_host"] = torch.zeros(1, dtype=torch.float32).pin_memory()
                 self.lib.check(self.lib.set_loss_host(p["handle"], ptr(p["loss_host"])))
         side = self.step_stream()
+        self._jitter_pass(p)
         if side is None:
             self.lib.check(self.lib.train_step(p["handle"], ptr(images), ptr(targets), ptr(p["loss"]), ptr(p["poses"]), None))
+            self._jitter_passed(p)
             self._stepped(p)
             return p["loss"], p["poses"].clone()
         cur = torch.cuda.current_stream(self.device)
@@ -359,6 +413,7 @@ class Engine:
                                                C.c_void_p(side.cuda_stream)))
             poses = p["poses"].clone()
         cur.wait_stream(side)
+        self._jitter_passed(p)
         self._stepped(p)
         return _StepLoss(self, p), poses
 

@@ -216,6 +216,12 @@ class PoseNet(_ArenaModule):
         (x/255 - mean)/std is applied by the conversion kernel.  `mean=None` restores fp32 [N,3,H,W] input."""
         self._engine.set_input_u8(mean, std)
 
+    def set_color_jitter(self, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, seed=0):
+        """torchvision's ColorJitter(brightness, contrast, saturation, hue) on the device, for uint8 input (set_input_u8), in every
+        forward pass -- train() and eval() alike, as the reference's transform jitters its validation set too.  All ranges 0 turns
+        it off.  Draws are keyed by `seed` and the model's count of jittered passes (include/mapnet_hip.h mn_set_color_jitter)."""
+        self._engine.set_color_jitter(brightness, contrast, saturation, hue, seed)
+
     def forward(self, x):
         u8 = self._engine.input_u8 is not None
         if x.dim() != 4 or (x.shape[-1] if u8 else x.shape[1]) != 3:
@@ -241,6 +247,9 @@ class MapNet(nn.Module):
 
     def set_input_u8(self, mean=None, std=None):
         self.mapnet.set_input_u8(mean, std)
+
+    def set_color_jitter(self, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, seed=0):
+        self.mapnet.set_color_jitter(brightness, contrast, saturation, hue, seed)
 
     def load_state_dict(self, state_dict, strict=True):
         r = super().load_state_dict(state_dict, strict)

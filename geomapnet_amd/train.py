@@ -102,6 +102,9 @@ def save_checkpoint(filename, epoch, model, optimizer, criterion):
     checkpoint_dict = {"epoch": epoch, "model_state_dict": model.state_dict(),
                        "optim_state_dict": optimizer.learner.state_dict(),
                        "criterion_state_dict": criterion.state_dict()}
+    eng = _jitter_engine(model)
+    if eng is not None and eng.jitter_active():  # (only then: the reference's dict otherwise)
+        checkpoint_dict["color_jitter_calls"] = eng.jitter_calls
     if filename is not None:
         torch.save(checkpoint_dict, filename)
     return checkpoint_dict
@@ -122,4 +125,14 @@ def load_checkpoint(checkpoint, model, optimizer=None, criterion=None, resume_op
             append_dict = {k: torch.Tensor([0.0]) for k, _ in criterion.named_parameters() if k not in c_state}
             c_state.update(append_dict)
             criterion.load_state_dict(c_state)
+        eng = _jitter_engine(model)
+        if eng is not None and "color_jitter_calls" in checkpoint:  # the device ColorJitter continues its draw sequence
+            eng.set_color_jitter_calls(checkpoint["color_jitter_calls"])
     return start_epoch
+
+
+def _jitter_engine(model):
+    try:
+        return engine_of(model)
+    except TypeError:
+        return None

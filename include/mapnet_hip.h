@@ -177,6 +177,25 @@ int mn_set_dropout_calls(mn_handle* h, uint32_t calls);
  * Cuts the host-to-device copy of a 192-image step from 201 MB to 50 MB. */
 int mn_set_input_u8(mn_handle* h, int enable, const float* mean, const float* std);
 
+/* ColorJitter on the device for uint8 input: replaces `transforms.ColorJitter(brightness=cj, contrast=cj, saturation=cj, hue=0.5)`,
+ * which the reference adds to its image transform when the config's color_jitter > 0 (scripts/train.py:58,121-125; train and
+ * validation sets alike).  Semantics: torchvision's ColorJitter on the float image x = u8 / 255 (its tensor implementation), then
+ * the Normalize of mn_set_input_u8.  Per image of every forward pass of a uint8 plan (mn_forward with training 0 or 1,
+ * mn_train_step, mn_train_forward_loss): factors b ~ U[max(0, 1-brightness), 1+brightness], c and s drawn the same way from
+ * contrast and saturation, h ~ U[-hue, hue], and a uniformly random order of the four ops (0 brightness: x = clamp(b x);
+ * 1 contrast: x = clamp(c x + (1-c) m), m the mean of gray(x) = 0.2989 r + 0.587 g + 0.114 b over the image as it stands at that
+ * point of its order; 2 saturation: x = clamp(s x + (1-s) gray(x)); 3 hue: H = (H + h) mod 1 in torchvision's HSV).  An op whose
+ * range is 0 is skipped; all four 0 = off (the default), and the forward pass is exactly the one without jitter.  Draws come from
+ * Philox4x32-10 with key `seed` and counter (image, jittered passes so far, a domain constant): reproducible, independent of
+ * launch shapes, readable after a pass as mn_debug_tensor "jitter" ([images][8] floats: b, c, s, h, then the op ids in the order
+ * applied; a skipped op reports 1, or 0 for hue).  Ranges must be finite and >= 0, hue <= 0.5.  A forward pass with jitter on
+ * and fp32 input fails: ColorJitter comes before Normalize, and fp32 frames arrive normalised.  Resets the pass count to 0. */
+int mn_set_color_jitter(mn_handle* h, float brightness, float contrast, float saturation, float hue, uint64_t seed);
+/* The Philox counter's "jittered passes so far" of this plan.  A host that runs several plans of one model (the last partial
+ * batch, validation batches) or resumes from a checkpoint sets it to the model's own count when a plan takes over, so that no plan
+ * replays the draws from 0; data-parallel ranks pass different seeds (scripts/train.py: seed ^ rank << 32). */
+int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls);
+
 /* replaces criterion(output, target) (common/train.py:351): loss only, on given predictions */
 int mn_loss(mn_handle* h, const float* pred, const float* targ, float* loss_out, void* stream);
 
@@ -362,6 +381,11 @@ int mn_op_maxpool_fwd(int dtype, const void* in, void* out, unsigned char* idx, 
                       void* stream);
 int mn_op_maxpool_bwd(int dtype, const unsigned char* idx, const void* gout, void* gin, int B, int H, int W, int C,
                       void* stream);
+/* the jittered input conversion of mn_set_color_jitter on its own: uint8 NHWC [B][H][W][3] -> fp32 NHWC4 [B][H+6][W+6][4] (padding
+ * 3 on every side), draws [B][8] as mn_debug_tensor "jitter", for pass `call` of `seed`.  ranges: brightness, contrast, saturation,
+ * hue; mean / std: 3 floats each in host memory; work: B * 9 floats of device memory (gray partials and means). */
+int mn_op_color_jitter(const unsigned char* in, float* out, float* draws, float* work, int B, int H, int W, const float* ranges,
+                       uint64_t seed, uint32_t call, const float* mean, const float* std, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (no counterpart in the reference, which is single-device: common/train.py:91-92).

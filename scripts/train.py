@@ -66,6 +66,10 @@ def build_parser():
                         "(default: a quarter of --synthetic_length)")
     parser.add_argument("--u8_input", action="store_true", help="frames as uint8 [H,W,3]; ToTensor + Normalize run on the "
                         "device (model.set_input_u8)")
+    parser.add_argument("--device_color_jitter", action="store_true",
+                        help="apply the config's color_jitter as torchvision's ColorJitter(cj, cj, cj, hue=0.5) on the device, "
+                             "to training and validation frames (the reference's transform, scripts/train.py:121-125); needs "
+                             "--u8_input.  Without this flag color_jitter is read and not applied")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     parser.add_argument("--epochs", type=int, default=None, help="override [training] n_epochs")
@@ -124,6 +128,7 @@ def run(args, datasets=None, _binding=None, log=print):
 
     section = settings["hyperparameters"]
     dropout = section.getfloat("dropout")
+    color_jitter = section.getfloat("color_jitter", 0)
     sax = 0.0
     saq = section.getfloat("beta")
     mapnet = args.model.find("mapnet") >= 0
@@ -152,6 +157,13 @@ def run(args, datasets=None, _binding=None, log=print):
 
     if args.u8_input:  # the DataLoader ships decoded frames; normalisation happens in the input-conversion kernel
         model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
+    if args.device_color_jitter and color_jitter > 0:
+        assert color_jitter <= 1.0
+        if not args.u8_input:
+            raise SystemExit("--device_color_jitter needs --u8_input: ColorJitter runs in the device's uint8 input conversion, "
+                             "before Normalize (fp32 frames arrive normalised)")
+        log("Using ColorJitter data augmentation")
+        model.set_color_jitter(color_jitter, color_jitter, color_jitter, 0.5, seed=seed ^ (_rank() << 32))
 
     # loss function
     if args.model == "posenet":
