@@ -7,15 +7,18 @@
 #pragma once
 #include <stdlib.h>
 #include "common.h"
+#include "knobs.h"
 #include "pool.h"
 
 namespace mn {
+
+constexpr long kBnReduceWgs = 512;  // workgroups of a BatchNorm-backward reduction (launch_bn_bwd explains)
 
 inline int ew_grid(long work_items) {
   // grid-stride kernels: at most 16 workgroups per CU.  (Measured and removed, same-box A/Bs of the whole step in
   // profiles/r02/c25_*: fewer workgroups per CU -- to leave wave slots to the weight gradients running beside the
   // HBM-bound passes -- and several pieces per thread for the small tensors of layers 3-4: no gain.)
-  static const long cap = getenv("MN_EW_WGS") ? atol(getenv("MN_EW_WGS")) : 256L * 16;  // (A/B knob)
+  constexpr long cap = 256L * 16;
   long b = (work_items + 255) / 256;
   if (b > cap) b = cap;
   if (b < 1) b = 1;
@@ -640,9 +643,9 @@ inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C,
   // ~512 workgroups (2 per CU): the reduction is HBM-bound and needs the whole chip, but every workgroup ends with an LDS
   // reduction and 2 x C fp64 atomics -- at 4096 workgroups (round 1) layers 3-4 did ONE loop iteration per workgroup and
   // that epilogue weighed as much as the loads (same-box A/Bs of the whole step: 4096 workgroups 17.77 ms,
-  // 1024 17.60, 512 17.42, 256 17.97; round 4, MN_BN_REDUCE_WGS: 512 / 768 / 1024 = 13.48 / 13.58 / 13.63 ms in fp16, equal within
+  // 1024 17.60, 512 17.42, 256 17.97; round 4: 512 / 768 / 1024 = 13.48 / 13.58 / 13.63 ms in fp16, equal within
   // 0.1 % on the fp16x2 mode's fp32 tensors, profiles/r04/c36_*)
-  static const long target = getenv("MN_BN_REDUCE_WGS") ? atol(getenv("MN_BN_REDUCE_WGS")) : 512;
+  constexpr long target = kBnReduceWgs;
   const int rlanes = 256 / (C / VEC);
   long rows = (M + target - 1) / target;
   rows = ((rows + rlanes - 1) / rlanes) * rlanes;
@@ -652,8 +655,8 @@ inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C,
   // (4 rows per thread per iteration in flight; 8 measured equal: 15.07 vs 14.99 ms per step)
   // rows in flight per thread: 2 for fp16 tensors (111 instead of 122 registers: one more wave fits beside the side stream's
   // weight gradient; 14.01 -> 13.89 ms per step), 4 for fp32 tensors (2: 30.74 -> 30.88 ms in the fp16x2 mode); profiles/r04/c11_*
-  static const bool pool_windows = !(getenv("MN_POOL_WINDOWS") && atoi(getenv("MN_POOL_WINDOWS")) == 0);
-  if (pg.idx && sizeof(T) == 4 && sizeof(TY) == 4 && self_gate_beta && pool_windows) {  // the stem on fp32 tensors: sums in pooled-window order
+  // the stem on fp32 tensors: sums in pooled-window order (profiles/r04/c32_stem_bn_sums_window_order_fp32.txt)
+  if (pg.idx && sizeof(T) == 4 && sizeof(TY) == 4 && self_gate_beta) {
     const long nwin = (long)(M / ((long)pg.H * pg.W)) * pg.Po * pg.Qo;
     long wrows = (nwin + target - 1) / target;
     wrows = ((wrows + rlanes - 1) / rlanes) * rlanes;
@@ -661,23 +664,20 @@ inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C,
                        reinterpret_cast<const float*>(pg.gout), pg.idx, reinterpret_cast<const float*>(y), mean, invstd, sg_gamma,
                        self_gate_beta, (int)(M / ((long)pg.H * pg.W)), pg.H, pg.W, pg.Po, pg.Qo, C, accum, (int)wrows, accum_rows);
   } else {
-  static const int reduce_u = getenv("MN_BN_REDUCE_U") ? atoi(getenv("MN_BN_REDUCE_U")) : (sizeof(T) == 2 ? 2 : 4);
+  constexpr int reduce_u = sizeof(T) == 2 ? 2 : 4;
   // (s_setprio 3 in the backward kernels, so that their waves are not starved by the weight gradient's MFMA waves on the same
   //  SIMD: no effect, 13.95 vs 14.00 ms fp16, 30.36 vs 30.38 ms fp16x2, profiles/r04/c12_*; removed)
   if (pg.idx)
     hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, 4, TY>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
                        rows_per_block, (float*)nullptr, sg_gamma, self_gate_beta, pg, accum_rows);
-  else if (reduce_u == 2)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, 2, TY>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
-                       rows_per_block, (float*)nullptr, sg_gamma, self_gate_beta, pg, accum_rows);
   else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, 4, TY>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, reduce_u, TY>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
                        rows_per_block, (float*)nullptr, sg_gamma, self_gate_beta, pg, accum_rows);
   }
 #ifdef MN_ABLATION_BUILD
   // timing experiment (results wrong): what the finalize launches of the units with at most MN_ABL_SKIP_FINALIZE channels cost a
   // step -- they run for the first 400 calls (coefficients of the warm-up steps stay in place), then are skipped
-  static const int skip_c = getenv("MN_ABL_SKIP_FINALIZE") ? atoi(getenv("MN_ABL_SKIP_FINALIZE")) : 0;
+  const int skip_c = knobs().abl_skip_finalize;
   static long calls = 0;
   if (!(C <= skip_c && ++calls > 400))
 #endif

@@ -397,20 +397,15 @@ inline void launch_bn_bwd_rec(const half* g, const half* rec, long M, int C, con
                               float* dgamma, float* dbeta, half* gy, double* accum, float* coef, float grad_unscale, hipStream_t s,
                               bool use_gate, int accum_rows) {
   constexpr int VEC = 8;
-  static const long target = getenv("MN_BN_REDUCE_WGS") ? atol(getenv("MN_BN_REDUCE_WGS")) : 512;  // (launch_bn_bwd explains)
+  constexpr long target = kBnReduceWgs;
   const int rlanes = 256 / (C / VEC);
   long rows = (M + target - 1) / target;
   rows = ((rows + rlanes - 1) / rlanes) * rlanes;
   if (rows < 4L * rlanes) rows = 4L * rlanes;
   const int rows_per_block = (int)rows;
   const int nblk = cdiv(M, rows_per_block);
-  static const int reduce_u = getenv("MN_BN_REDUCE_U") ? atoi(getenv("MN_BN_REDUCE_U")) : 4;
-  if (reduce_u == 2)
-    hipLaunchKernelGGL((bn_bwd_reduce_rec_kernel<2>), dim3(nblk), dim3(256), 0, s, g, rec, M, C, accum, rows_per_block, use_gate ? 1 : 0,
-                       accum_rows);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_rec_kernel<4>), dim3(nblk), dim3(256), 0, s, g, rec, M, C, accum, rows_per_block, use_gate ? 1 : 0,
-                       accum_rows);
+  hipLaunchKernelGGL((bn_bwd_reduce_rec_kernel<4>), dim3(nblk), dim3(256), 0, s, g, rec, M, C, accum, rows_per_block, use_gate ? 1 : 0,
+                     accum_rows);
   hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, (const double*)accum, (double)M, gamma, mean,
                      invstd, dgamma, dbeta, grad_unscale, (const float*)nullptr, coef, C, accum_rows);
   const long np = M * C / VEC;

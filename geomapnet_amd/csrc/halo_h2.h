@@ -319,18 +319,18 @@ static __global__ void __launch_bounds__(256, 1) conv_halo_h2_kernel(GatherGeom 
 // +100, halo DMA +30-60, stores +40, and they ADD in either form although the LDS array is busy a sixth of the time and conflict-free
 // (SQ_LDS_BANK_CONFLICT = 0, SQ_LDS_IDX_ACTIVE 4.15 cycles per read): what a memory instruction costs here is its ISSUE, ~40 cycles
 // of a CU's wave time per ds_read_b128, and a second wave per SIMD does not hide it.)
-// persistent workgroups: one per CU (MN_HALO_H2_WGS overrides), at most one per tile
+// persistent workgroups: knobs().halo_h2_wgs (one per CU), at most one per tile
 inline int conv_halo_h2_grid(const GatherGeom& g) {
   const int ntiles = g.B * cdiv(g.P, kH2TH) * cdiv(g.Q, kH2TW);
-  static const int wgs_env = getenv("MN_HALO_H2_WGS") ? atoi(getenv("MN_HALO_H2_WGS")) : 256;
-  return ntiles < wgs_env ? ntiles : wgs_env;
+  const int wgs = knobs().halo_h2_wgs;
+  return ntiles < wgs ? ntiles : wgs;
 }
 inline void launch_conv_halo_h2(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream) {
   const int tx = cdiv(g.Q, kH2TW), ty = cdiv(g.P, kH2TH);
   const int ntiles = g.B * tx * ty;
   const dim3 grid(conv_halo_h2_grid(g));
 #ifdef MN_ABLATION_BUILD
-  static const int abl = getenv("MN_HALO_H2_ABLATE") ? atoi(getenv("MN_HALO_H2_ABLATE")) : 0;
+  const int abl = knobs().halo_h2_ablate;
   {
 #define H2_CASE(V_) case V_: hipLaunchKernelGGL((conv_halo_h2_kernel<true, V_, 1, 2>), grid, dim3(256), 0, stream, g, A, Bw, ep, tx, ty, ntiles); return
   switch (abl) {

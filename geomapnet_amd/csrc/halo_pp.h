@@ -353,16 +353,15 @@ inline bool conv_halo_pp_applies(const GatherGeom& g, const Epilogue& ep) {
          (long)g.B * g.P * g.Q * ep.ldc * (ep.gate_h2 ? 4L : 2L) < 0x7ffffff0l;  // (masked lanes use offset 2^31)
 }
 
-// wgs: persistent workgroups (0 = one per CU, or MN_HALO_PP_WGS)
+// wgs: persistent workgroups (0 = knobs().halo_pp_wgs: one per CU)
 inline void launch_conv_halo_pp(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream,
                                 int wgs_arg = 0) {
   const int tx = cdiv(g.Q, kHaloTW), ty = cdiv(g.P, kHaloTH);
   const int ntiles = g.B * tx * ty;
-  static const int wgs_env = getenv("MN_HALO_PP_WGS") ? atoi(getenv("MN_HALO_PP_WGS")) : 256;  // one per CU
-  const int wgs = wgs_arg > 0 ? wgs_arg : wgs_env;
+  const int wgs = wgs_arg > 0 ? wgs_arg : knobs().halo_pp_wgs;
   const dim3 grid(ntiles < wgs ? ntiles : wgs);
 #ifdef MN_ABLATION_BUILD
-  static const int abl = getenv("MN_HALO_PP_ABLATE") ? atoi(getenv("MN_HALO_PP_ABLATE")) : 0;
+  const int abl = knobs().halo_pp_ablate;
 #define PP_CASE(S, A_, P_) hipLaunchKernelGGL((conv_halo_pp_kernel<S, A_, P_>), grid, dim3(512), 0, stream, g, A, Bw, ep, tx, ty, ntiles); return
 #define PP_VAR(S, PD_, E_) hipLaunchKernelGGL((conv_halo_pp_kernel<S, 0, 0, PD_, E_>), grid, dim3(512), 0, stream, g, A, Bw, ep, tx, ty, ntiles); return
   if (ep.stats_accum) {

@@ -859,22 +859,12 @@ static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherG
 // upper bound of the number of M-blocks a launch uses (sizes the BatchNorm partial buffer)
 inline int igemm_grid_m(int M) { return cdiv(M, 128); }
 
-// Tile configurations (per-shape choice in launch_igemm; MN_IGEMM_CONFIG=1|8|12 forces one -- the parity tests use it to
-// run the 12-wave tile on small ragged problems):
+// Tile configurations (per-shape choice in launch_igemm; knobs().igemm_config = 1|8|12 forces one):
 //   1: 128x128 / 128x64 (N <= 64), 4 waves of 64x64 / 64x32, 128-byte K-steps, 2 buffers   (2 workgroups/CU)
 //   8: 256x128, 4 waves of 128x64, 64-byte K-steps, 3 buffers                              (2 workgroups/CU)
 //  12: 288x256, 12 waves of 96x64, 128-byte K-steps, 2 buffers                             (1 workgroup/CU)
 // Measured alternatives that lost everywhere and were removed: 3-4 workgroups/CU (64-byte steps), deeper rings,
 // 256x64 tiles for N = 64, 8-wave 256x128 and 256x256 tiles, 256x256 tiles of 128x128 wave tiles, 576x128 tiles.
-inline int igemm_config() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MN_IGEMM_CONFIG");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-
 inline int device_cus() {  // compute units of the current device (256 on MI355X)
   static int v = 0;
   if (v == 0) {
@@ -922,10 +912,8 @@ inline int maybe_launch_igemm_halo(const GatherGeom&, const T*, const T*, const 
 template <>
 inline int maybe_launch_igemm_halo<half>(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep,
                                          hipStream_t stream, bool tile288_wanted) {
-  // measured on MI355X (round 2, same-box A/B of the whole step): level 0 17.34 ms, 1 (256-column shape: layer3) 17.03,
-  // 2 (+ 128-column shape: layers 2 and 4) 16.79; per launch layer2 114 -> 104, layer3 93 -> 81, layer4 112 -> 87 us.
-  // MN_IGEMM_HALO=0|1 (parity tests: the generic kernel on the same shapes)
-  static const int level = getenv("MN_IGEMM_HALO") ? atoi(getenv("MN_IGEMM_HALO")) : 2;
+  // (per launch, level 0 -> 2: layer2 114 -> 104, layer3 93 -> 81, layer4 112 -> 87 us)
+  const int level = knobs().igemm_halo;
   return level > 0 ? launch_igemm_halo(g, A, Bw, ep, stream, level, tile288_wanted) : -1;
 }
 
@@ -939,7 +927,7 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
   // 98 -> 92 us, with residual 117 -> 107, layer2 120 -> 117
   g.tap_inner = (g.R * g.S > 1 || g.bt_on) ? 1 : 0;
   const bool wide_k = (g.C / VEC) % 8 == 0;  // 128-byte K-steps need taps that are a multiple of them
-  int cfg = igemm_config();
+  int cfg = knobs().igemm_config;
   if constexpr (sizeof(T) == 4) {
     // x3 modes: 128-row tiles of 4 waves, two workgroups per CU (the split operands and the raw pieces need the 256
     // registers that occupancy leaves a wave)
@@ -961,8 +949,7 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
       }
 #ifdef MN_ABLATION_BUILD
       if (wide_k) {
-        static const int abl = getenv("MN_ABLATE") ? atoi(getenv("MN_ABLATE")) : 0;
-        switch (abl) {
+        switch (knobs().ablate) {
           case 1: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 1>(g, A, Bw, ep, stream, zero_page);
           case 2: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 2>(g, A, Bw, ep, stream, zero_page);
           case 3: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 3>(g, A, Bw, ep, stream, zero_page);
@@ -1014,7 +1001,7 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
   // residual 111.7 -> 103.6; the same change costs the 128x128 configuration 5 %, so it is not used there).
   if (cfg == 12 && wide_k && g.N % 256 == 0 && g.R * g.S <= 10) {  // (packed tap masks: 10 bits per A pass)
 #ifdef MN_ABLATION_BUILD
-    static const int abl = getenv("MN_ABLATE") ? atoi(getenv("MN_ABLATE")) : 0;
+    const int abl = knobs().ablate;
     if (abl == 1) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 1>(g, A, Bw, ep, stream, zero_page);
     if (abl == 2) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 2>(g, A, Bw, ep, stream, zero_page);
     if (abl == 3) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 3>(g, A, Bw, ep, stream, zero_page);
@@ -1038,13 +1025,9 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
 inline bool conv_halo_h2_applies(const GatherGeom& g, const Epilogue& ep);
 inline int conv_halo_h2_grid(const GatherGeom& g);
 inline void launch_conv_halo_h2(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream);
-inline bool use_conv_halo_h2() {  // MN_HALO_H2=0: the chunk-resident 64-column shape of igemm_halo.h (A/B measurements)
-  static const bool on = !(getenv("MN_HALO_H2") && atoi(getenv("MN_HALO_H2")) == 0);
-  return on;
-}
 inline int launch_igemm_h2(const GatherGeom& g_in, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream,
                            const half* zero_page, bool q = false) {
-  if (!q && use_conv_halo_h2() && conv_halo_h2_applies(g_in, ep)) {
+  if (!q && conv_halo_h2_applies(g_in, ep)) {
     launch_conv_halo_h2(g_in, A, Bw, ep, stream);
     return conv_halo_h2_grid(g_in);
   }
@@ -1057,8 +1040,7 @@ inline int launch_igemm_h2(const GatherGeom& g_in, const half* A, const half* Bw
   RowDiv rd;
   rd.q = make_fastdiv(g.Q);
   rd.p = make_fastdiv(g.P);
-  static const int halo_level = getenv("MN_IGEMM_HALO") ? atoi(getenv("MN_IGEMM_HALO")) : 2;
-  if (halo_level > 0) {
+  if (knobs().igemm_halo > 0) {
     const int gm_halo = launch_igemm_halo_h2(g, A, Bw, ep, stream);
     if (gm_halo >= 0) return gm_halo;
   }

@@ -508,7 +508,7 @@ inline bool igemm_halo_applies(const GatherGeom& g, const Epilogue& ep, int bn, 
          (long)g.M * g.C * 2 < 0xfffffff0l && (long)g.N * g.K * 2 < 0xfffffff0l && !ep.om_on;
 }
 
-// MN_IGEMM_HALO: 1 = the 256-column shape where igemm.h would pick its own 288x256 tile (layer3 at 192 images, or a
+// level (knobs().igemm_halo): 1 = the 256-column shape where igemm.h would pick its own 288x256 tile (layer3 at 192 images, or a
 // forced MN_IGEMM_CONFIG=12); 2 = additionally the 128-column shape for every other launch it covers (layers 2 and 4).
 // Returns the number of M-blocks used (rows of a [grid_m][2][N] statistics buffer), or -1 if the launch is not taken.
 inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream,
@@ -518,11 +518,12 @@ inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw,
   rd.q = make_fastdiv(g.Q);
   rd.p = make_fastdiv(g.P);
 #ifdef MN_ABLATION_BUILD
-  static const int abl = getenv("MN_HALO_ABLATE") ? atoi(getenv("MN_HALO_ABLATE")) : 0;
+  const int abl = knobs().halo_ablate;
 #endif
-  // (MN_HALO_A1_F16: the same switch for the plain-fp16 launches alone -- in the fp16x2m mode those are the data gradients, whose
-  //  70 KB form leaves room for a weight-gradient workgroup of the side stream on the same CU: A/B knob)
-  static const int a1 = getenv("MN_HALO_A1_F16") ? atoi(getenv("MN_HALO_A1_F16")) : (getenv("MN_HALO_A1") ? atoi(getenv("MN_HALO_A1")) : 1);
+  // (the 192-row tile switched off for the plain-fp16 launches alone -- in the fp16x2m mode those are the data gradients, whose 70 KB
+  //  form shares a CU with a weight-gradient workgroup of the side stream: measured, not kept,
+  //  profiles/r06/c21_c22_co_residency_and_xcd_order_experiments.txt)
+  const int a1 = knobs().halo_a1;
   if (level >= 1 && tile288_wanted && a1 != 2 && igemm_halo_applies(g, ep, 256, 352)) {
 #ifdef MN_ABLATION_BUILD
 #define MN_HALO_ABL(BN_, AH_, V_)                                                                                          \
@@ -544,7 +545,7 @@ inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw,
   // against the 8-wave 384-row tile below: fp16 forward 90.8 -> 90.1 us, data gradient 87.5 -> 84.2, with residual 110.9 -> 105.8,
   // step 13.22 -> 13.16 ms; fp16x2 224 -> 202, 218 -> 199, 282 -> 250 us, step 28.82 -> 28.55 ms (profiles/r04/c30_*).
   // For layers 3 and 4 (704 / 352 such tiles: 1.4 / 0.7 rounds) it loses to their one-round shapes: fp16 76 -> 85 and 81 -> 88 us,
-  // fp16x2 191 -> 207 and 223 -> 234 us (call 31).  MN_HALO_A1: 0 off, 2 always (parity tests)
+  // fp16x2 191 -> 207 and 223 -> 234 us (call 31).  a1 (knobs().halo_a1): 0 off, 2 always
   if (level >= 2 && a1 > 0 && (a1 == 2 || (long)cdiv(g.M, 192) * (g.N / 128) >= 2L * device_cus()) &&
       igemm_halo_applies(g, ep, 128, 288, 192)) {
     hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, false, 2, 2, true>), dim3(cdiv(g.M, 192) * (g.N / 128)), dim3(256), 0, stream, g,
@@ -555,8 +556,8 @@ inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw,
   //  for halo_pp.h's persistent kernel with resident weights; whole step 13.32 -> 13.63 ms, profiles/r04/c34_*)
   // the 8-wave 384-row tile of 96 x 64 wave tiles where it fills the chip's rounds as well as the 288-row tile does (layer2 at 192
   // images: 688 tiles = 2.69 rounds against 918 = 3.59): 0.55 instead of 0.89 fragment reads per MFMA; layer2 forward 99.3 -> 92.7
-  // us, data gradient 97.2 -> 90.5, whole step 13.95 -> 13.79 ms (round 4, profiles/r04/c28_*).  MN_HALO384: 0 never, 2 always.
-  static const int bm384 = getenv("MN_HALO384") ? atoi(getenv("MN_HALO384")) : 1;
+  // us, data gradient 97.2 -> 90.5, whole step 13.95 -> 13.79 ms (round 4, profiles/r04/c28_*).  bm384: 0 never, 2 always.
+  const int bm384 = knobs().halo384;
   if (level >= 2 && bm384 > 0 && igemm_halo_applies(g, ep, 128, 480, 384)) {
     const long t384 = (long)cdiv(g.M, 384) * (g.N / 128), t288 = (long)gm * (g.N / 128);
     const int cus = device_cus();
@@ -596,8 +597,8 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
   rd.q = make_fastdiv(g2.Q);
   rd.p = make_fastdiv(g2.P);
   const long tiles288 = (long)gm * (g2.N / 256);
-  static const bool force256 = getenv("MN_H2_HALO256") && atoi(getenv("MN_H2_HALO256")) != 0;  // (parity tests on small problems)
-  static const int a1 = getenv("MN_HALO_A1") ? atoi(getenv("MN_HALO_A1")) : 1;  // (see launch_igemm_halo)
+  const bool force256 = knobs().h2_halo256;
+  const int a1 = knobs().halo_a1;  // (see launch_igemm_halo)
   if (g2.N % 256 == 0 && ((tiles288 > 192 && tiles288 <= device_cus()) || force256) && igemm_halo_applies(g2, ep, 256, 352)) {
     if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<256, 352, 0, 1, true, 3, 4, false, 1, true>), dim3(gm * (g2.N / 256)), dim3(768), 0, stream, g2, A, Bw, ep,
@@ -608,10 +609,9 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
     return gm;
   }
   // layer1 (64 -> 64 channels, rows of up to 87 pixels): 192-row tiles of 4 waves, one A image, two workgroups per CU
-  static const bool halo64 = !(getenv("MN_H2_HALO64") && atoi(getenv("MN_H2_HALO64")) == 0);
   // (measured: 338 -> 304 us forward, 356 -> 326 data gradient, step 29.69 -> 29.52 ms; 288-row tiles of 6 waves at two workgroups
   //  per CU -- 27 % less DMA per row -- 409 us: six waves do not spread over four SIMDs; profiles/r04/c15_*, c16_*)
-  if (halo64 && g2.N == 64 && igemm_halo_applies(g2, ep, 64, 368, 192)) {
+  if (g2.N == 64 && igemm_halo_applies(g2, ep, 64, 368, 192)) {
     if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<64, 368, 0, 1, true, 2, 2, true, 2, true>), dim3(cdiv(g2.M, 192)), dim3(256), 0, stream, g2, A, Bw, ep, 1,
                        rd);
@@ -633,12 +633,11 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
   }
   // 128-column layers: the 8-wave 384-row tile where it fills the chip's rounds about as well as the 288-row tile does (layer2 at
   // 192 images: 688 tiles = 2.69 rounds against 918 = 3.59; layer4: 176 tiles = 0.69 of a round against 236 = 0.92 -> 288 rows)
-  static const int bm384 = getenv("MN_H2_HALO384") ? atoi(getenv("MN_H2_HALO384")) : 1;  // 0: never, 1: by tile count, 2: always
-  if (bm384 > 0 && igemm_halo_applies(g2, ep, 128, 480, 384)) {
+  if (igemm_halo_applies(g2, ep, 128, 480, 384)) {
     const long t384 = (long)cdiv(g2.M, 384) * (g2.N / 128), t288 = (long)gm * (g2.N / 128);
     const int cus = device_cus();
     const double e384 = (double)t384 / ((double)cdiv(t384, cus) * cus), e288 = (double)t288 / ((double)cdiv(t288, cus) * cus);
-    if (bm384 == 2 || e384 >= e288 - 0.03) {
+    if (e384 >= e288 - 0.03) {
     if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, true, 4, 2, false, 1, true>), dim3(cdiv(g2.M, 384) * (g2.N / 128)), dim3(512), 0, stream, g2,
                          A, Bw, ep, g2.N / 128, rd);

@@ -16,6 +16,7 @@
 #include "elementwise_h2.h"
 #include "head.h"
 #include "jitter.h"
+#include "knobs.h"
 #include "dense.h"
 #include "igemm.h"
 #include "dgrad.h"
@@ -116,31 +117,12 @@ struct PlanBase {
     static hipStream_t streams[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    // (a side stream of lower or higher priority was measured: no gain)
-    // MN_WGRAD_CUS=n (experiment, round 5): the side stream may only use n of the chip's CUs (hipExtStreamCreateWithCUMask) -- a
-    // static partition, so that weight-gradient workgroups cannot take every CU away from the main stream's BatchNorm /
-    // data-gradient launches.  MN_WGRAD_CU_SPREAD=1 spreads the n CUs evenly over the mask's bit range instead of taking the first
-    // n.  Measured: profiles/r05 (cu mask); not a default.
-    if (!streams[dev]) {
-      const int ncu = getenv("MN_WGRAD_CUS") ? atoi(getenv("MN_WGRAD_CUS")) : 0;
-      int total = 0;
-      hipDeviceGetAttribute(&total, hipDeviceAttributeMultiprocessorCount, dev);
-      hipError_t e;
-      if (ncu > 0 && total > 0 && ncu < total) {
-        const bool spread = getenv("MN_WGRAD_CU_SPREAD") && atoi(getenv("MN_WGRAD_CU_SPREAD")) != 0;
-        std::vector<uint32_t> mask((total + 31) / 32, 0u);
-        for (int i = 0; i < ncu; ++i) {
-          const int bit = spread ? (int)((long)i * total / ncu) : i;
-          mask[bit / 32] |= 1u << (bit % 32);
-        }
-        e = hipExtStreamCreateWithCUMask(&streams[dev], (uint32_t)mask.size(), mask.data());
-      } else {
-        e = hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking);
-      }
-      if (e != hipSuccess) {
-        streams[dev] = nullptr;
-        (void)hipGetLastError();
-      }
+    // (a side stream of lower or higher priority was measured: no gain.  A side stream restricted to n of the chip's CUs
+    //  (hipExtStreamCreateWithCUMask), so that weight-gradient workgroups cannot take every CU away from the main stream's
+    //  BatchNorm / data-gradient launches: measured and removed, profiles/r05 (cu mask))
+    if (!streams[dev] && hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking) != hipSuccess) {
+      streams[dev] = nullptr;
+      (void)hipGetLastError();
     }
     return streams[dev];
   }
@@ -152,7 +134,7 @@ struct PlanBase {
   std::vector<hipEvent_t> fork_events;
   size_t fork_next = 0;
   bool wgrad_pending = false;
-  bool overlap_wgrad = !(getenv("MN_WGRAD_STREAM") && atoi(getenv("MN_WGRAD_STREAM")) == 0);
+  bool overlap_wgrad = knobs().wgrad_stream;
   hipEvent_t next_fork_event() {
     if (fork_events.size() < 64) {
       hipEvent_t e = nullptr;
@@ -247,7 +229,7 @@ struct PlanBase {
   int64_t stuck_skips = 0;        // CONSECUTIVE skips seen while the scale already was 1 (nothing left to lower); an APPLIED
                                   // step, a scale growth or mn_set_loss_scale resets it
   long long clean_steps = 0;      // applied steps since the last skip the host has seen
-  int scale_growth_interval = getenv("MN_SCALE_GROWTH") ? atoi(getenv("MN_SCALE_GROWTH")) : 2000;
+  int scale_growth_interval = knobs().scale_growth;
   // The host reads the pinned words WITHOUT waiting for the device, so a poll that sees no new skip proves nothing by itself: the
   // host may simply be ahead (C-API callers that never read the loss, DataLoader jitter).  Progress is only what the device reports:
   // overflow_host[3], the index of the last attempt it completed.  (Round-4 ADVICE: the previous form reset `stuck_skips` and
@@ -362,7 +344,7 @@ struct Plan : PlanBase {
   // that does not depend on scheduling: BatchNorm sums through one accumulator row per producing workgroup (below),
   // weight gradients through per-split workspace slices and an ordered reduction (conv_wgrad), the gradient norm through
   // per-workgroup partial sums (optim.h).  Costs ~x ms per step.
-  const bool deterministic = getenv("MN_DETERMINISTIC") && atoi(getenv("MN_DETERMINISTIC")) != 0;
+  const bool deterministic = knobs().deterministic;
   static constexpr int ACC_ROWS = 8;  // (32 rows measured equal: 14.73 vs 14.69 ms per step)
   double* acc_region = nullptr;
   size_t acc_bytes = 0;
@@ -398,13 +380,13 @@ struct Plan : PlanBase {
       // finalize kernels add the rows in a fixed order.  Forward producers: the stem kernel's persistent workgroups, the
       // layer1 kernel's persistent workgroups (halo_pp.h: at most one per 16x16-pixel tile), M-tiles of >= 128 rows elsewhere.
       if (is_stem)
-        u.rows_f = use_stem_kernel && (DT == MN_F16 || mma_fwd == MMA_F16X3) ? 1024 : cdiv((int)u.M, 128);
+        u.rows_f = (DT == MN_F16 || mma_fwd == MMA_F16X3) ? 1024 : cdiv((int)u.M, 128);
       else if (halo_path(u.gf))
         u.rows_f = u.gf.B * cdiv(u.gf.P, kHaloTH) * cdiv(u.gf.Q, kHaloTW);
       else
         u.rows_f = cdiv((int)u.M, 128);
       // (layer1's h2 convolutions on the persistent register-resident-weight kernel, halo_h2.h: one row per workgroup)
-      if (h2 && !q8 && !is_stem && use_conv_halo_h2() && u.cp.k == 3 && u.cp.stride == 1 && u.cp.cin == 64 && u.cp.cout == 64) {
+      if (h2 && !q8 && !is_stem && u.cp.k == 3 && u.cp.stride == 1 && u.cp.cin == 64 && u.cp.cout == 64) {
         const int wgs = conv_halo_h2_grid(u.gf);
         if (u.rows_f < wgs) u.rows_f = wgs;
       }
@@ -457,7 +439,7 @@ struct Plan : PlanBase {
       for (Unit* u : us) {
         if (!u) continue;
         unit_bufs(*u);
-        if (use_rec) u->rec = (half*)A((size_t)u->M * u->cp.cout * sizeof(half));
+        if (mixed) u->rec = (half*)A((size_t)u->M * u->cp.cout * sizeof(half));
         size_t wn = (size_t)u->cp.cout * u->cp.cin * u->cp.k * u->cp.k;
         if (DT == MN_F16 || h2)
           u->wf = (T*)A(wn * sizeof(T));  // (h2: 4 bytes per element as well)
@@ -545,13 +527,11 @@ struct Plan : PlanBase {
   // values": by default (stem_f16) its two backward kernels (stem_bwd.h) read an fp16 copy of the fp32 conv output (written by the
   // stem's BatchNorm + max-pool pass) and an fp16 image of the input, so its BatchNorm-backward sums and xhat come from fp16-rounded
   // y; only its ReLU gate stays exact (the pooled gradient arrives already gated by layer1.0's data gradient).  MN_DETERMINISTIC=1
-  // or MN_STEM_BWD=0 keep the fp32 chain of fp16x2 for the stem.
+  // keeps the fp32 chain of fp16x2 for the stem.
   bool mixed = false;
   // fp16x2m, round 6: BatchNorm's backward pass reads a 2-byte RECORD of the forward pass (fp16 xhat + the ReLU's outcome in its
   // lowest bit, written by the forward apply) instead of the 4-byte conv output -- 2 bytes per element more in one forward pass, 2
-  // fewer in each of the two backward passes, and the gate stays exact.  MN_BN_REC=0: round 5's form (fp32 conv output re-read, gate
-  // recomputed), for same-box A/Bs.
-  bool use_rec = false;
+  // fewer in each of the two backward passes, and the gate stays exact (Unit::rec; profiles/r06/c4_batchnorm_backward_from_a_record.txt).
   // MN_DTYPE_F16X2Q (round 5; Plan<float> only): fp16x2m whose FORWARD convolutions take both cross terms of a split-operand product
   // from fp8 copies on the block-scaled MFMA (common.h MMA_H2Q, h2q tensors): 2 instead of 3 MFMA-equivalents per forward product,
   // poses ~3e-4 from the fp32 reference instead of 1.6e-5 (bar 1e-3)
@@ -563,21 +543,16 @@ struct Plan : PlanBase {
     q8 = DT == MN_F32 && c.dtype == MN_DTYPE_F16X2Q;
     mixed = DT == MN_F32 && (c.dtype == MN_DTYPE_F16X2M || q8);
     h2 = DT == MN_F32 && (c.dtype == MN_DTYPE_F16X2 || mixed);
-    stem_f16 = mixed && !deterministic && !(getenv("MN_STEM_BWD") && atoi(getenv("MN_STEM_BWD")) == 0);
-    use_rec = mixed && !(getenv("MN_BN_REC") && atoi(getenv("MN_BN_REC")) == 0);
+    stem_f16 = mixed && !deterministic;
     if (c.dtype == MN_DTYPE_F32X3 || h2) {  // (fp16x2m: the stem's backward and its fp32 tensors)
       mma_fwd = MMA_F16X3;
       mma_bwd = MMA_BF16X3;
     }
-    overflow_guard = (DT == MN_F16 || h2) && !(getenv("MN_OVERFLOW_GUARD") && atoi(getenv("MN_OVERFLOW_GUARD")) == 0);
-    // (fp16x2m: 0 / 1 / 2 measured equal in round 5; with round 6's shorter BatchNorm-backward passes 1 leads by 0.3 %: 18.96 / 19.02 /
-    //  19.15 ms for 1 / 0 / 2, two interleaved repeats, profiles/r06/c6_*)
-    // (fp16: one fork per block since round 4; round 6, with the per-stage choices below: 13.10 -> 13.00 ms, four of four interleaved
-    //  pairs, profiles/r06/c52_to_c54_*)
-    if (!getenv("MN_WGRAD_SCHED") && early_fork) wgrad_sched = (mixed || h2 || DT == MN_F16) ? 1 : 2;  // (see wgrad_sched)
-    const bool staged_choice = mixed || (DT == MN_F16 && !h2);
-    if (!getenv("MN_WGRAD_EARLY_STAGES") && staged_choice) wgrad_early_stages = 13;  // (see wgrad_early_stages)
-    if (!getenv("MN_WGRAD_DEFER_STAGES") && staged_choice) wgrad_defer_stages = 2;   // (see wgrad_defer_stages)
+    overflow_guard = DT == MN_F16 || h2;
+    const WgradSchedule ws = resolve_wgrad_schedule(knobs(), h2 || DT == MN_F16, mixed || DT == MN_F16);
+    wgrad_sched = ws.sched;
+    wgrad_early_stages = ws.early_stages;
+    wgrad_defer_stages = ws.defer_stages;
     L = Layout(c.feat_dim);
     frames = (c.mode == MN_MODE_POSENET) ? 1 : (c.mode == MN_MODE_MAPNET ? c.T : 2 * c.T);
     B = c.windows * frames;
@@ -767,9 +742,9 @@ struct Plan : PlanBase {
     auto* tp = timer.begin(0, s);
     if (h2 && &u != &stem)  // h2 activation and weights in, fp32 conv output + statistics out
       launch_igemm_h2(u.gf, (const half*)x, (const half*)u.wf, ep, s, (const half*)zero_page, q8);
-    else if (&u == &stem && DT == MN_F32 && mma_fwd == MMA_F16X3 && use_stem_kernel)  // the split-operand form of the stem kernel
+    else if (&u == &stem && DT == MN_F32 && mma_fwd == MMA_F16X3)  // the split-operand form of the stem kernel
       launch_stem_conv_x3((const float*)x, (const float*)u.wf, (float*)u.y, training ? u.accum_f : nullptr, u.rows_f, B, H, W, Wp, s);
-    else if (&u == &stem && DT == MN_F16 && use_stem_kernel)  // weights in registers, input pairs read straight from LDS (stem.h)
+    else if (&u == &stem && DT == MN_F16)  // weights in registers, input pairs read straight from LDS (stem.h)
       launch_stem_conv((const half*)x, (const half*)u.wf, (half*)u.y, training ? u.accum_f : nullptr, u.rows_f, B, H, W, Wp, s);
     else if (halo_path(u.gf) && conv_halo_pp_applies(u.gf, ep))
       launch_conv_halo_pp(u.gf, (const half*)x, (const half*)u.wf, ep, s);
@@ -778,16 +753,11 @@ struct Plan : PlanBase {
     timer.end(tp, s);
   }
   // layer1's 64-channel 3x3 convolutions (forward and data gradient) run from an LDS-resident input halo in the
-  // persistent two-group kernel of halo_pp.h (MN_HALO=0: the implicit-GEMM kernel, for A/B measurements)
-  bool use_halo = DT == MN_F16 && !(getenv("MN_HALO") && atoi(getenv("MN_HALO")) == 0);
-  bool use_halo_bwd = !(getenv("MN_HALO") && atoi(getenv("MN_HALO")) == 0);  // fp16x2m: layer1's data gradients
-  bool use_stem_kernel = !(getenv("MN_STEM_KERNEL") && atoi(getenv("MN_STEM_KERNEL")) == 0);
-  // MN_DENSE=0: the head's fc layer through igemm.h's 128 x 128 tiles (parity tests, A/B)
-  bool use_dense = !(getenv("MN_DENSE") && atoi(getenv("MN_DENSE")) == 0);
-  bool halo_path(const GatherGeom& g) const { return use_halo && conv_halo_applies(g); }
+  // persistent two-group kernel of halo_pp.h; the shapes it does not cover go to the implicit-GEMM kernel
+  bool halo_path(const GatherGeom& g) const { return DT == MN_F16 && conv_halo_applies(g); }
   void bn_finalize(Unit& u, hipStream_t s) {  // statistics -> (scale, shift), mean / invstd, running statistics
 #ifdef MN_ABLATION_BUILD
-    static const int skip_c = getenv("MN_ABL_SKIP_FINALIZE") ? atoi(getenv("MN_ABL_SKIP_FINALIZE")) : 0;  // (see launch_bn_bwd)
+    const int skip_c = knobs().abl_skip_finalize;  // (see launch_bn_bwd)
     static long calls = 0;
     if (u.cp.cout <= skip_c && ++calls > 400) return;
 #endif
@@ -869,10 +839,7 @@ struct Plan : PlanBase {
       // The projection path of a down block (1x1 stride-2 convolution, BatchNorm) depends on the block's input only: it runs on the
       // side stream -- idle in the forward pass -- beside conv1 -> bn1 -> conv2 and is joined before the residual add.  Three blocks,
       // ~0.25 ms of small launches: fp16x2m 18.18 -> 18.05 ms, four of four interleaved pairs (profiles/r06/c41_c42_*).
-      // MN_FWD_DS_SIDE=0: in line, as before (A/B).
-      static const bool ds_side = !(getenv("MN_FWD_DS_SIDE") && atoi(getenv("MN_FWD_DS_SIDE")) == 0);
-      const bool side = blk.down && ds_side;
-      if (side) {
+      if (blk.down) {
         hipStream_t ws = fork_wgrad(s);
         conv_bn_stats(blk.ud, blk.x, training, ws);
         bn_act(blk.ud, nullptr, 0, blk.zd, ws);
@@ -882,12 +849,7 @@ struct Plan : PlanBase {
       conv_bn_stats(blk.u2, blk.a1, training, s);
       const T* res = blk.x;
       if (blk.down) {
-        if (side) {
-          join_wgrad(s);
-        } else {
-          conv_bn_stats(blk.ud, blk.x, training, s);
-          bn_act(blk.ud, nullptr, 0, blk.zd, s);
-        }
+        join_wgrad(s);
         res = blk.zd;
       }
       bn_act(blk.u2, res, 1, blk.out, s);
@@ -912,7 +874,7 @@ struct Plan : PlanBase {
     DenseArgs da;
     da.A = pooled; da.W = params + L.fc_w; da.bias = params + L.fc_b; da.C = feat; da.M = B; da.N = F; da.K = 512; da.lda = 512;
     da.ldw = 512; da.ldc = F; da.relu = 1;
-    if (use_dense && dense_nt_applies(da))  // 32 x 32 tiles, K split over the workgroup's waves (dense.h)
+    if (dense_nt_applies(da))  // 32 x 32 tiles, K split over the workgroup's waves (dense.h)
       launch_dense_nt(da, s);
     else
       launch_igemm<float>(g, (const float*)pooled, (const float*)(params + L.fc_w), ep, s, (const float*)zero_page);
@@ -981,10 +943,10 @@ struct Plan : PlanBase {
   }
   // bit 0: BatchNorm+ReLU+max-pool in one forward pass (-0.15 ms/step); bit 1: max-pool gradient gathered inside the
   // BatchNorm backward passes instead of a maxpool_bwd launch (measured +0.05 ms/step: the gather runs twice) -- off
-  int fuse_stem_mask = getenv("MN_FUSE_STEM") ? atoi(getenv("MN_FUSE_STEM")) : 1;
+  int fuse_stem_mask = knobs().fuse_stem;
   bool fuse_stem = (fuse_stem_mask & 1) != 0;
   bool fuse_stem_bwd = (fuse_stem_mask & 2) != 0;
-  bool early_fork = !(getenv("MN_EARLY_FORK") && atoi(getenv("MN_EARLY_FORK")) == 0);
+  bool early_fork = knobs().early_fork;
   static constexpr bool parity_dgrad = true;  // stride-2 data gradients by parity class (dgrad.h: -1.6 % step time)
   // `ws`: the stream the launch goes to (the side stream after a fork, or the main stream)
   void conv_wgrad(Unit& u, const T* x, hipStream_t ws) {
@@ -1017,7 +979,7 @@ struct Plan : PlanBase {
     auto* tp = timer.begin(0, s);
     if (mixed) {  // the fp16 mode's launches: fp16 d(conv output), weights, gradient and residual; the gate = hi halves of the h2 activation
       ep.gate_h2 = true;
-      if (use_halo_bwd && conv_halo_applies(u.dg.full) && conv_halo_pp_applies(u.dg.full, ep))
+      if (conv_halo_applies(u.dg.full) && conv_halo_pp_applies(u.dg.full, ep))
         launch_conv_halo_pp(u.dg.full, (const half*)u.gy, (const half*)u.wd, ep, s);
       else
         launch_conv_dgrad<half>(u.dg, (const half*)u.gy, (const half*)u.wd, ep, s, (const half*)zero_page, parity_dgrad);
@@ -1029,29 +991,12 @@ struct Plan : PlanBase {
       launch_conv_dgrad<T>(u.dg, (const T*)u.gy, (const T*)u.wd, ep, s, (const T*)zero_page, parity_dgrad);
     timer.end(tp, s);
   }
-  // Weight-gradient schedule (MN_WGRAD_SCHED): 0 = one fork per block, after its last BatchNorm backward;
-  // 1 = each weight gradient forked as soon as its dY exists (starts beside the data gradient that consumes the
-  // same dY); 2 = deferred: a weight gradient is queued and forked right before the NEXT BatchNorm-backward pass of
-  // the main stream, so that the MFMA-bound launch starts beside HBM-bound work instead of beside a data gradient.
-  // Round 2 (fused weight gradient: one 512-thread, 96 KB workgroup per CU -- it does not share a CU with a data-gradient
-  // workgroup, the two time-slice): 1 = 16.44 ms, 0 = 16.05, 2 = 16.01 (same-box A/B); round 1's plain-GEMM weight gradient
-  // preferred 1.  Round 4, after the fused weight gradient moved to its low-register forms (134 / 150 registers, 64 KB of LDS:
-  // BatchNorm waves and, in part, other workgroups now fit beside it) the order turned over, same-box A/Bs, arms interleaved twice
-  // (profiles/r04/c43_*): fp16 2 = 13.14 ms, 1 = 13.01, 0 = 12.98; fp16x2 2 = 28.60, 1 = 28.02, 0 = 28.38.  Defaults since:
-  // fp16 0, fp16x2 1 (set in the constructor), fp32 / fp32x3 2 (not re-measured).
-  int wgrad_sched = getenv("MN_WGRAD_SCHED") ? atoi(getenv("MN_WGRAD_SCHED")) : (early_fork ? 2 : 0);
-  // (block_backward.  Same-box A/Bs, arms interleaved, profiles/r06/c29_to_c32_*: fp16x2m 0 -> 1: -0.04 ... -0.10 ms in six of six pairs
-  //  (18.37 -> 18.31), 2: equal, 3: +0.06; fp16 12.78 -> 12.73.  3 with the stem's weight gradient at ONE workgroup per CU
-  //  (MN_STEM_WGRAD_PER_CU=1, which alone costs +0.35 ms) is within 0.03 ms of 1.)
-  int wgrad_tail = getenv("MN_WGRAD_TAIL") ? atoi(getenv("MN_WGRAD_TAIL")) : 1;
-  // MN_WGRAD_EARLY_STAGES: bit k = schedule 1's early fork applies to stage k (else one fork per block, schedule 0's order).  fp16x2m
-  // (set in the constructor): 13 = every stage but layer2, whose data gradients run in the 70 KB two-workgroup form and share their
-  // CUs with whatever the side stream brings -- 18.61 -> 18.55 ms, six of six interleaved pairs (profiles/r06/c35_to_c37_*).
-  int wgrad_early_stages = getenv("MN_WGRAD_EARLY_STAGES") ? atoi(getenv("MN_WGRAD_EARLY_STAGES")) : 15;
-  // MN_WGRAD_DEFER_STAGES: bit k = stage k takes schedule 2's order (a weight gradient queued and forked right before the NEXT
-  // BatchNorm-backward pass) whatever the plan's schedule is.  fp16x2m (set in the constructor): 2 = layer2 -- against one fork per
-  // block there: 18.25 -> 18.20 ms, six of six interleaved pairs; layer4 +0.17, layer3 +0.05, layer1 +0.05 (profiles/r06/c38_to_c40_*).
-  int wgrad_defer_stages = getenv("MN_WGRAD_DEFER_STAGES") ? atoi(getenv("MN_WGRAD_DEFER_STAGES")) : 0;
+  // Weight-gradient schedule: the knobs, the per-mode defaults and their measurements are in knobs.h (resolve_wgrad_schedule);
+  // set in the constructor, once the mode is known
+  int wgrad_sched = 0;
+  int wgrad_tail = knobs().wgrad_tail;
+  int wgrad_early_stages = 15;
+  int wgrad_defer_stages = 0;
   struct PendingWgrad {
     Unit* u;
     const T* x;
@@ -1147,9 +1092,9 @@ struct Plan : PlanBase {
                        (const float*)feat, (const float*)(params + L.xyz_w), (const float*)(params + L.wpqr_w), dz, B, F,
                        cfg.filter_nans, drop_this_step ? (const float*)dropmask : (const float*)nullptr);
     // The head's and the fc layer's WEIGHT gradients feed nothing downstream: with two streams they leave with the first fork of the
-    // backward pass (fork_wgrad), off the chain criterion -> heads -> fc -> average pool -> layer4 (MN_HEAD_WGRAD_SIDE=0: in line)
-    static const bool head_side = !(getenv("MN_HEAD_WGRAD_SIDE") && atoi(getenv("MN_HEAD_WGRAD_SIDE")) == 0);
-    if (head_side && overlap_wgrad && s != nullptr && !timer.enabled)
+    // backward pass (fork_wgrad), off the chain criterion -> heads -> fc -> average pool -> layer4 (-0.02 ms, four of four
+    // pairs, profiles/r06/c43_*)
+    if (overlap_wgrad && s != nullptr && !timer.enabled)
       head_wgrads_deferred = true;
     else
       launch_head_wgrads(s);
@@ -1164,7 +1109,7 @@ struct Plan : PlanBase {
     DenseArgs dd;
     dd.A = dz; dd.W = fcT; dd.bias = nullptr; dd.C = dpooled; dd.M = B; dd.N = 512; dd.K = F; dd.lda = F; dd.ldw = F; dd.ldc = 512;
     dd.relu = 0;
-    if (use_dense && dense_nt_applies(dd))
+    if (dense_nt_applies(dd))
       launch_dense_nt(dd, s);
     else
       launch_igemm<float>(gd, (const float*)dz, (const float*)fcT, ep, s, (const float*)zero_page);
@@ -1180,10 +1125,10 @@ struct Plan : PlanBase {
                          (const float*)dpooled, last.gout, B, Hl * Wl, 512, (const T*)last.out, 0);
   }
   // (MN_DETERMINISTIC: the stem's backward goes through bn_bwd + the split-slice weight gradient instead)
-  bool use_stem_bwd = DT == MN_F16 && !deterministic && !(getenv("MN_STEM_BWD") && atoi(getenv("MN_STEM_BWD")) == 0);
+  bool use_stem_bwd = DT == MN_F16 && !deterministic;
   // fp16x2m: the same two kernels on fp16 COPIES of the fp32 conv output (written by the stem's BatchNorm + max-pool pass) and of
-  // the padded input, with the pooled gradient arriving already gated (StemBwdArgs::pre_gated); MN_STEM_BWD=0 / MN_DETERMINISTIC
-  // keep the fp32 chain of fp16x2
+  // the padded input, with the pooled gradient arriving already gated (StemBwdArgs::pre_gated); MN_DETERMINISTIC
+  // keeps the fp32 chain of fp16x2
   bool stem_f16 = false;  // (set in the constructor, once `mixed` is known)
   bool stem_bwd_f16() const { return stem_f16; }
   void stem_backward(hipStream_t s) {
@@ -1384,6 +1329,7 @@ static int validate(const mn_config* c) {
 
 extern "C" int64_t mn_plan_bytes(const mn_config* cfg) {
   if (validate(cfg)) return -1;
+  load_knobs();
   if (cfg->dtype == MN_DTYPE_F16) {
     Plan<half> p(*cfg);
     return (int64_t)p.carve(nullptr);
@@ -1401,6 +1347,7 @@ extern "C" mn_handle* mn_create(const mn_config* cfg, float* params, float* opt_
   }
   mn_handle* h = new mn_handle();
   begin_call();
+  load_knobs();
   int rc;
   if (cfg->dtype == MN_DTYPE_F16) {
     auto* p = new Plan<half>(*cfg);

@@ -8,6 +8,7 @@
 #include "elementwise.h"
 #include "head.h"
 #include "jitter.h"
+#include "knobs.h"
 #include "dense.h"
 #include "igemm.h"
 #include "dgrad.h"
@@ -33,6 +34,12 @@ extern "C" const char* mn_last_error(void) { return mn::g_last_error.c_str(); }
 #define MN_BACKEND_NAME "hip"
 #endif
 extern "C" const char* mn_backend(void) { return MN_BACKEND_NAME; }
+
+// entry of a stand-alone operator: the knob table follows the environment of THIS call (knobs.h, read rule)
+static void begin_op() {
+  begin_call();
+  load_knobs();
+}
 
 static GatherGeom to_geom(const mn_gather_geom* g) {
   GatherGeom r;
@@ -62,7 +69,7 @@ extern "C" int mn_op_igemm_grid_m(int M) { return igemm_grid_m(M); }
 extern "C" int mn_op_igemm(int dtype, const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc,
                            float* stats, const float* bias, int relu, const void* res, const void* res_gate, float alpha,
                            const void* zero_page, void* stream) {
-  begin_call();
+  begin_op();
   GatherGeom g = to_geom(gg);
   if (int e = check_geom(g, dtype)) return e;
   if (!zero_page) return fail("igemm: zero_page (>= 16 zero bytes of device memory) is required");
@@ -89,7 +96,7 @@ extern "C" int mn_op_igemm(int dtype, const mn_gather_geom* gg, const void* A, c
 extern "C" int mn_op_conv_halo_pp(const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
                                  int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate,
                                  float alpha, int wgs, void* stream) {
-  begin_call();
+  begin_op();
   GatherGeom g = to_geom(gg);
   if (int e = check_geom(g, MN_F16)) return e;
   Epilogue ep;
@@ -106,7 +113,7 @@ static int op_wgrad(int dtype, const mn_gather_geom* gg, const void* dY, int ldy
                     void* stream);
 extern "C" int mn_op_conv_halo_h2(const mn_gather_geom* gg, const void* A, const void* Bw, float* out, int ldc, double* stats_accum,
                                   int stats_rows, void* stream) {
-  begin_call();
+  begin_op();
   GatherGeom g = to_geom(gg);
   if (int e = check_geom(g, MN_DTYPE_F16X2)) return e;
   Epilogue ep;
@@ -131,7 +138,7 @@ extern "C" int mn_op_wgrad_ws(int dtype, const mn_gather_geom* gg, const void* d
 static int op_wgrad(int dtype, const mn_gather_geom* gg, const void* dY, int ldy, const void* X, float* dW, int ldw,
                     const int32_t* colmap, float alpha, int target_blocks, const void* zero_page, float* ws, long ws_floats,
                     void* stream) {
-  begin_call();
+  begin_op();
   WgradArgs a;
   a.ws = ws;
   a.ws_floats = ws_floats;
@@ -151,7 +158,7 @@ static int op_wgrad(int dtype, const mn_gather_geom* gg, const void* dY, int ldy
 
 extern "C" int mn_op_stem_conv(const void* xpad, const void* wf, void* y, double* stats_accum, int stats_rows, int B, int H, int W,
                                int Wp, void* stream) {
-  begin_call();
+  begin_op();
   if (Wp % 2 != 0 || Wp < W + 7) return fail("stem_conv: Wp must be even and >= W + 7");
   if ((long)B * (H + 6) * Wp * 8 >= 0xfffffff0l) return fail("stem_conv: padded input exceeds 4 GiB");
   launch_stem_conv((const half*)xpad, (const half*)wf, (half*)y, stats_accum, stats_rows, B, H, W, Wp, (hipStream_t)stream);
@@ -160,14 +167,14 @@ extern "C" int mn_op_stem_conv(const void* xpad, const void* wf, void* y, double
 
 extern "C" int mn_op_stem_conv_x3(const float* xpad, const float* wf, float* y, double* stats_accum, int stats_rows, int B, int H,
                                   int W, int Wp, void* stream) {
-  begin_call();
+  begin_op();
   if (Wp % 2 != 0 || Wp < W + 7) return fail("stem_conv_x3: Wp must be even and >= W + 7");
   launch_stem_conv_x3(xpad, wf, y, stats_accum, stats_rows, B, H, W, Wp, (hipStream_t)stream);
   return check_launch("stem_conv_x3");
 }
 
 extern "C" int mn_op_dense(const float* A, const float* W, const float* bias, float* C, int M, int N, int K, int relu, void* stream) {
-  begin_call();
+  begin_op();
   DenseArgs a;
   a.A = A; a.W = W; a.bias = bias; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldc = N; a.relu = relu;
   if (M <= 0 || N <= 0 || !dense_nt_applies(a)) return fail("dense: K must be a multiple of 128, A and W 16-byte aligned");
@@ -177,7 +184,7 @@ extern "C" int mn_op_dense(const float* A, const float* W, const float* bias, fl
 
 extern "C" int mn_op_dense_wgrad(const float* dY, const float* X, float* dW, float* db, int B, int F, int Cin, float alpha,
                                  void* stream) {
-  begin_call();
+  begin_op();
   if (B <= 0 || F <= 0 || Cin <= 0) return fail("dense_wgrad: empty problem");
   DenseWgradArgs a;
   a.dY = dY; a.X = X; a.dW = dW; a.db = db; a.B = B; a.F = F; a.Cin = Cin; a.ldy = F; a.ldx = Cin; a.ldw = Cin; a.alpha = alpha;
@@ -187,7 +194,7 @@ extern "C" int mn_op_dense_wgrad(const float* dY, const float* X, float* dW, flo
 
 extern "C" int mn_op_head_wgrad(const float* dposes, const float* feat, float* dWx, float* dbx, float* dWq, float* dbq, int B, int K,
                                 float scale, int filter_nans, void* stream) {
-  begin_call();
+  begin_op();
   if (B <= 0 || K <= 0) return fail("head_wgrad: empty problem");
   hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(cdiv(K + 1, 64)), dim3(256), 0, (hipStream_t)stream, dposes, feat, dWx, dbx, dWq,
                      dbq, B, K, scale, filter_nans);
@@ -198,7 +205,7 @@ extern "C" int mn_op_stem_bwd(const void* y, const unsigned char* idx, const voi
                               const float* mean, const float* invstd, const void* xpad, float* dW, int ldw, const int32_t* colmap,
                               float* dgamma, float* dbeta, float* coef_scratch, double* accum_scratch, int B, int H, int W, int Wp,
                               float alpha, void* stream) {
-  begin_call();
+  begin_op();
   if (Wp % 2 != 0 || Wp < W + 7) return fail("stem_bwd: Wp must be even and >= W + 7");
   hipStream_t s = (hipStream_t)stream;
   const int H0 = (H - 1) / 2 + 1, W0 = (W - 1) / 2 + 1;
@@ -215,7 +222,7 @@ extern "C" int mn_op_stem_bwd(const void* y, const unsigned char* idx, const voi
 }
 
 extern "C" int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, int H, int W, int to_ohwi, void* stream) {
-  begin_call();
+  begin_op();
   hipLaunchKernelGGL(oihw_ohwi_kernel, dim3(ew_grid((long)O * I * H * W)), dim3(256), 0, (hipStream_t)stream, src, dst, O,
                      I, H, W, to_ohwi);
   return check_launch("oihw_ohwi");
@@ -223,7 +230,7 @@ extern "C" int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, in
 
 extern "C" int mn_op_criterion(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss,
                                float* dpred, float* ds, float* vos_out, float grad_scale, void* stream) {
-  begin_call();
+  begin_op();
   if (T < 1 || T > kMaxT) return fail("criterion: T out of range");
   if (mode < 0 || mode > 3) return fail("criterion: bad mode");
   CriterionArgs a;
@@ -235,7 +242,7 @@ extern "C" int mn_op_criterion(int mode, int N, int T, const float* pred, const 
 
 extern "C" int mn_op_calc_vos(const float* poses, int N, int T, float* vos, const float* cot, float* dposes,
                               void* stream) {
-  begin_call();
+  begin_op();
   if (T < 2 || T > kMaxT) return fail("calc_vos: T out of range");
   hipLaunchKernelGGL(calc_vos_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, poses, N, T, vos, cot,
                      dposes);
@@ -245,7 +252,7 @@ extern "C" int mn_op_calc_vos(const float* poses, int N, int T, float* vos, cons
 extern "C" int mn_op_conv_dgrad(int dtype, int B, int Hin, int Win, int Cin, int Cout, int k, int stride, int pad,
                                const void* gy, const void* wd, void* gx, const void* res, const void* res_gate,
                                const void* out_gate, int parity, const void* zero_page, void* stream) {
-  begin_call();
+  begin_op();
   if (stride != 1 && stride != 2) return fail("conv_dgrad: stride must be 1 or 2");
   if (k < 1 || k > 5 || pad < 0 || pad >= k) return fail("conv_dgrad: kernel / padding out of range");
   if (!zero_page) return fail("conv_dgrad: zero_page (>= 16 zero bytes of device memory) is required");
@@ -274,7 +281,7 @@ extern "C" int mn_op_conv_dgrad(int dtype, int B, int Hin, int Win, int Cin, int
 
 extern "C" int mn_pgo_optimize(const double* poses, const double* vos, double* out, int32_t* status, int W, int N,
                                int fc_vos, double sax, double saq, double srx, double srq, int n_iters, void* stream) {
-  begin_call();
+  begin_op();
   if (W <= 0) return fail("pgo: no windows");
   if (N < 2 || N > kPgoMaxN) return fail("pgo: 2 <= poses per window <= 12");
   if (!(sax > 0.0 && saq > 0.0 && srx > 0.0 && srq > 0.0)) return fail("pgo: covariances must be positive");
@@ -299,7 +306,7 @@ extern "C" int mn_op_adam(float* p, const float* g, float* m, float* v, int64_t 
 extern "C" int mn_op_optim(int method, int nesterov, float* p, const float* g, float* m, float* v, int64_t n, int64_t n_clip,
                            float lr, float wd, float beta1, float beta2, float eps, int64_t step, float grad_mul, float max_norm,
                            double* sqnorm_scratch, int eps_mode, void* stream) {
-  begin_call();
+  begin_op();
   if (method < 0 || method > 2) return fail("optim: method must be 0 (adam), 1 (sgd) or 2 (rmsprop)");
   hipStream_t s = (hipStream_t)stream;
   if (max_norm > 0.f) {
@@ -351,7 +358,7 @@ static int check_bn_channels(int dtype, int C) {
 extern "C" int mn_op_bn_train_fwd(int dtype, const void* y, int64_t M, int C, const float* gamma, const float* beta,
                                   float* running_mean, float* running_var, float* mean, float* invstd, const void* res,
                                   int relu, void* out, float eps, float momentum, double* accum_scratch, void* stream) {
-  begin_call();
+  begin_op();
   if (int e = check_bn_channels(dtype, C)) return e;
   if (dtype == MN_F16)
     return bn_train_fwd_t<half>(y, M, C, gamma, beta, running_mean, running_var, mean, invstd, res, relu, out, eps,
@@ -374,7 +381,7 @@ static int bn_bwd_t(const void* g, const void* gate, const void* y, int64_t M, i
 extern "C" int mn_op_bn_bwd(int dtype, const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma,
                             const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy,
                             float* coef_scratch, double* accum_scratch, float grad_unscale, void* stream) {
-  begin_call();
+  begin_op();
   if (int e = check_bn_channels(dtype, C)) return e;
   hipMemsetAsync(accum_scratch, 0, 2 * C * sizeof(double), (hipStream_t)stream);
   if (dtype == MN_F16)
@@ -386,7 +393,7 @@ extern "C" int mn_op_bn_bwd(int dtype, const void* g, const void* gate, const vo
 
 extern "C" int mn_op_maxpool_fwd(int dtype, const void* in, void* out, unsigned char* idx, int B, int H, int W, int C,
                                  void* stream) {
-  begin_call();
+  begin_op();
   int Po = (H + 2 - 3) / 2 + 1, Qo = (W + 2 - 3) / 2 + 1;
   if (dtype == MN_F16)
     hipLaunchKernelGGL((maxpool_fwd_kernel<half>), dim3(ew_grid((long)B * Po * Qo * C / 8)), dim3(256), 0,
@@ -399,7 +406,7 @@ extern "C" int mn_op_maxpool_fwd(int dtype, const void* in, void* out, unsigned 
 
 extern "C" int mn_op_maxpool_bwd(int dtype, const unsigned char* idx, const void* gout, void* gin, int B, int H, int W,
                                  int C, void* stream) {
-  begin_call();
+  begin_op();
   int Po = (H + 2 - 3) / 2 + 1, Qo = (W + 2 - 3) / 2 + 1;
   if (dtype == MN_F16)
     hipLaunchKernelGGL((maxpool_bwd_kernel<half>), dim3(ew_grid((long)B * H * W * C / 8)), dim3(256), 0,
@@ -412,7 +419,7 @@ extern "C" int mn_op_maxpool_bwd(int dtype, const unsigned char* idx, const void
 
 extern "C" int mn_op_occupy(int workgroups, int threads, float microseconds, const void* src, void* dst, int64_t bytes, int lds_kb,
                             void* stream) {
-  begin_call();
+  begin_op();
   if (workgroups < 1 || workgroups > 4096 || threads < 64 || threads > 1024 || threads % 64 != 0)
     return fail("mn_op_occupy: 1..4096 workgroups of 64..1024 threads (a multiple of 64)");
   if (!(microseconds >= 0.f) || microseconds > 1e6f) return fail("mn_op_occupy: 0 <= microseconds <= 1e6");
@@ -425,7 +432,7 @@ extern "C" int mn_op_occupy(int workgroups, int threads, float microseconds, con
 extern "C" int mn_op_color_jitter(const unsigned char* in, float* out, float* draws, float* work, int B, int H, int W,
                                   const float* ranges, uint64_t seed, uint32_t call, const float* mean, const float* std,
                                   void* stream) {
-  begin_call();
+  begin_op();
   if (B < 1 || H < 1 || W < 1 || !in || !out || !draws || !work || !ranges || !mean || !std)
     return fail("mn_op_color_jitter: B, H, W >= 1 and every pointer required");
   InputNorm nm;

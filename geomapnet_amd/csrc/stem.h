@@ -167,7 +167,7 @@ inline void launch_stem_conv(const half* xpad, const half* wf, half* y, double* 
   a.H0 = (H - 1) / 2 + 1; a.W0 = (W - 1) / 2 + 1;
   a.tiles_x = cdiv(a.W0, kStemTW); a.tiles_y = cdiv(a.H0, kStemTH);
   // persistent: two workgroups per CU (the 220-register kernel's occupancy), each walking tiles blockIdx.x, + grid, ...
-  static const int wgs = getenv("MN_STEM_WGS") ? atoi(getenv("MN_STEM_WGS")) : 512;
+  const int wgs = knobs().stem_wgs > 0 ? knobs().stem_wgs : 512;
   const int ntiles = B * a.tiles_x * a.tiles_y;
   hipLaunchKernelGGL(stem_conv_kernel, dim3(ntiles < wgs ? ntiles : wgs), dim3(256), 0, stream, a);
 }
@@ -358,7 +358,7 @@ inline void launch_stem_conv_x3(const float* xpad, const float* wf, float* y, do
   a.B = B; a.Hp = H + 6; a.Wp2 = Wp / 2;
   a.H0 = (H - 1) / 2 + 1; a.W0 = (W - 1) / 2 + 1;
   a.tiles_x = cdiv(a.W0, kStemTW); a.tiles_y = cdiv(a.H0, kStemTH);
-  static const int wgs = getenv("MN_STEM_WGS") ? atoi(getenv("MN_STEM_WGS")) : 512;
+  const int wgs = knobs().stem_wgs > 0 ? knobs().stem_wgs : 512;
   const int ntiles = B * a.tiles_x * a.tiles_y;
   hipLaunchKernelGGL(stem_conv_x3_kernel, dim3(ntiles < wgs ? ntiles : wgs), dim3(256), 0, stream, a);
 }

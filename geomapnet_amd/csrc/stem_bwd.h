@@ -404,7 +404,7 @@ inline void stem_bwd_geometry(StemBwdArgs& a, int B, int H, int W, int Wp) {
   a.tiles_x = cdiv(a.W0, kSbTW); a.tiles_y = cdiv(a.H0, kSbTH);
 }
 inline int stem_bwd_grid(const StemBwdArgs& a, int per_cu) {
-  static const int wgs = getenv("MN_STEM_WGS") ? atoi(getenv("MN_STEM_WGS")) : 0;
+  const int wgs = knobs().stem_wgs;
   const int want = wgs > 0 ? wgs : 256 * per_cu;
   const int ntiles = a.B * a.tiles_x * a.tiles_y;
   return ntiles < want ? ntiles : want;
@@ -413,13 +413,13 @@ inline int stem_bwd_grid(const StemBwdArgs& a, int per_cu) {
 inline void launch_stem_bn_reduce(StemBwdArgs a, int B, int H, int W, int Wp, hipStream_t stream) {
   stem_bwd_geometry(a, B, H, W, Wp);
   const int ntiles = a.B * cdiv(a.Po, kSrPH) * cdiv(a.Qo, kSrPW);  // (tiles of pooled windows; one workgroup per CU)
-  static const int wgs = getenv("MN_STEM_WGS") ? atoi(getenv("MN_STEM_WGS")) : 0;
+  const int wgs = knobs().stem_wgs;
   const int want = wgs > 0 ? wgs : 256;
   hipLaunchKernelGGL(stem_bn_reduce_kernel, dim3(ntiles < want ? ntiles : want), dim3(512), 0, stream, a);
 }
 inline void launch_stem_wgrad(StemBwdArgs a, int B, int H, int W, int Wp, hipStream_t stream) {
   stem_bwd_geometry(a, B, H, W, Wp);
-  static const int per_cu = getenv("MN_STEM_WGRAD_PER_CU") ? atoi(getenv("MN_STEM_WGRAD_PER_CU")) : 2;  // (A/B knob)
+  constexpr int per_cu = 2;  // (one workgroup per CU: +0.35 ms per step, profiles/r06/c29_to_c32_*)
   hipLaunchKernelGGL(stem_wgrad_kernel, dim3(stem_bwd_grid(a, per_cu)), dim3(256), 0, stream, a);
 }
 

@@ -773,7 +773,7 @@ struct WgradDma<half> {
 };
 
 // wgrad_fused.h: 3x3 stride-1 fp16 layers with the nine taps of a channel tile accumulated from one LDS-resident pass
-// over the pixels (MN_WGRAD_FUSED=0 restores the plain GEMM form below for them)
+// over the pixels (knobs().wgrad_fused = false: the plain GEMM form below for them)
 inline bool wgrad_fused_applies(const WgradArgs& a);
 inline bool wgrad_fused_x3_applies(const WgradArgs& a);
 inline bool wgrad_fused_h2_applies(const WgradArgs& a);
@@ -793,7 +793,7 @@ inline void launch_zero_fill(float* p, long n, hipStream_t s);  // optim.h
 template <typename T>
 inline void launch_wgrad(WgradArgs a, int target_blocks, hipStream_t stream, const void* zero_page = nullptr) {
   const GatherGeom& g = a.g;
-  static const bool fused = !(getenv("MN_WGRAD_FUSED") && atoi(getenv("MN_WGRAD_FUSED")) == 0);
+  const bool fused = knobs().wgrad_fused;
   if constexpr (ElemTraits<T>::DTYPE == MN_F16) {
     if (g.mma == MMA_H2) {  // h2 tensors: the DMA-fed tap-fused kernel, or (stride-2 / 1x1 shapes) the generic loader
       if (fused && wgrad_fused_h2_applies(a)) {
@@ -810,13 +810,12 @@ inline void launch_wgrad(WgradArgs a, int target_blocks, hipStream_t stream, con
       return;
     }
   }
-  static const bool stem_wide = !(getenv("MN_STEM_WGRAD_WIDE") && atoi(getenv("MN_STEM_WGRAD_WIDE")) == 0);
   bool narrow_k = g.K <= 64 || (g.K % 128 != 0 && g.K < 256);
   // the stem's weight gradient on fp32 tensors (K = 224 columns): two 128-column tiles read the 1 GB d(conv output) twice,
   // four 64-column tiles four times
   // (ONE 256-column tile, d(conv output) read once: 29.55 vs 29.57 ms per step -- the launch runs on the side stream, which is not
   //  the critical path; measured and not kept, round 4 call 33)
-  if (stem_wide && sizeof(T) == 4 && g.mma == MMA_BF16X3 && g.K > 128) narrow_k = false;
+  if (sizeof(T) == 4 && g.mma == MMA_BF16X3 && g.K > 128) narrow_k = false;
   const bool narrow_n = g.N <= 64;
   int bmo = narrow_n ? 64 : 128, bno = narrow_k ? 64 : 128;
   int tiles = cdiv(g.N, bmo) * cdiv(g.K, bno);

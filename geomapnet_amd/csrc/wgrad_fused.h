@@ -52,276 +52,12 @@ struct WgradFusedArgs {
   bool x_h2 = false; // (round 6) X is an h2 tensor of which the hi halves are read (WgradArgs::x_h2); wgrad_fused_h2_kernel<.., LO = false>
 };
 
-// LDS rows of the X ring: (D+1) steps + 2 Gpad; bounds the image width (Gpad <= 96 -> Q <= 94, i.e. inputs up to 376
-// pixels wide at layer1).  4-wave form: 32-row steps; 8-wave form: 64-row steps.
-constexpr int WGF_RING_MAX8 = 448;
-
-// 8 waves = 512 threads, 64-pixel steps, one workgroup per CU.  Wave roles: 32-column block of the 64 input channels (wc),
-// pixel half of every step (grp: rows 0-31 / 32-63 -- split-K inside the workgroup: at the end the two halves are added
-// through LDS, so a CU flushes ONE partial tile; the partial-tile volume of a launch, what the reduce launch has to read
-// back, is the number of resident accumulator tiles x 147 KB = 38 MB) and tap half (tset: taps 0-4 or 5-8).  A wave owns
-// BOTH 32-row blocks of the 64 output channels for its taps, so a B fragment (X rows at the tap's shift) feeds TWO MFMAs:
-// 1.4 fragment-read instructions per MFMA and one address add + one counted wait per two MFMAs.  Waves w and w + 4 (one
-// SIMD) hold the 5-tap and the 4-tap half: 18 MFMAs per SIMD per K sub-step.
-// (Round 2's form gave a wave one output-channel block for all nine taps -- a B fragment per MFMA, 2.2 read instructions
-// per MFMA.  Same time per launch in isolation, 101-109 us at every layer, so the loop is NOT issue-bound as round 2
-// concluded; the whole step runs 0.8 % faster with this form beside the other stream's kernels, 14.45 vs 14.60 ms,
-// profiles/r03/c8_*.  A 4-wave form -- two 256-thread workgroups per CU, twice the partial tiles -- was slower and is gone.)
-// ABL (timing experiments only, MN_WGF_ABLATE in the ablation build; results are wrong): bit 0 = no DMA after the prologue,
-// bit 1 = no B-fragment reads, bit 2 = no MFMA, bit 3 = no stores / atomics.
-// PD: B fragments requested ahead of the MFMAs that consume them.
-// DPI: the LDS-DMA of step s + D is issued behind the MFMAs of item DPI of step s (-1: right after the barrier, rounds 1-2).
-// Measured per launch at layers 1-4 (profiles/r03/c14_*, c15_*): -1: 112 / 105 / 101 / 109 us, 1: 111 / 101 / 98 / 106,
-// 4: 111 / 103 / 99 / 108, 7: 108 / 101 / 97 / 105, 8: 110 / 109 / 102 / 109, 9: 116 / 112 / 106 / 114; whole step 13.94 (-1) vs
-// 13.85 ms (7) on one box -- right after the barrier the requests (and the address arithmetic of their pixels) compete with
-// every wave's first fragment reads.
-// (Measured and removed, round 3, profiles/r03/c9_*: a ROTATED loop -- the A fragments and the first PD B fragments of step
-// s + 1 requested at the end of step s, in flight across the barrier, for which step s + 1 has to be visible one barrier
-// early, i.e. one DMA step fewer in flight -- 101-109 -> 106-115 us per launch, step 14.49 -> 14.59 ms.)
-// No item ever wraps around the ring: the 64 rows behind the ring mirror its first block (the DMA that fills block 0 is
-// issued twice), so a tap window that starts near the end simply runs on into the mirror.
-template <int D, int ABL = 0, int PD = 3, int DPI = 7>
-static __global__ void __launch_bounds__(512, 2) wgrad_fused_kernel(WgradFusedArgs a) {
-  constexpr int NW = 8;
-  static_assert(D >= 1 && D <= 3, "steps in flight");
-  constexpr int BKM = 8 * NW;              // pixels per step = one DMA pass of all threads per operand
-  constexpr int ROWH = 64;                 // halves per LDS row (64 channels / 64 output channels)
-  constexpr int TILE_Y = BKM * ROWH;       // halves
-  constexpr int NY = D + 1;                // dY tiles
-  constexpr int RING_MAX = WGF_RING_MAX8;
-  // ONE LDS object: [NY dY tiles][X ring (RING rows used)][mirror of ring rows 0 .. BKM-1, right behind row RING-1]
-  __shared__ half smem[NY * TILE_Y + (RING_MAX + BKM) * ROWH] __attribute__((aligned(16)));
-  half* ring = &smem[NY * TILE_Y];
-
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wc = wave & 1, grp = (wave >> 1) & 1, tset = wave >> 2;  // 32-column block of the 64 inputs; pixel half; tap half
-  const int tap0 = tset * 5, ntap = tset == 0 ? 5 : 4;
-  // logical id = (chunk, pair): the pairs of one pixel range are adjacent, i.e. on one XCD, and share its L2 lines
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int pairs = a.tiles_n * a.tiles_c;
-  const int ci = logical / pairs, pr = logical - ci * pairs;
-  const int n0 = (pr / a.tiles_c) * 64, c0 = (pr % a.tiles_c) * 64;
-  const int j0 = ci * a.chunk;
-  const int j1 = min(a.J, j0 + a.chunk);
-  const int nsteps = (j1 - j0 + BKM - 1) / BKM;
-  const int Gpad = a.Gpad, RING = a.ring;
-
-  const __amdgpu_buffer_rsrc_t rsrc_y = make_rsrc(a.dY, (long)a.B * a.P * a.Q * a.ldy * 2L);
-  const __amdgpu_buffer_rsrc_t rsrc_x = make_rsrc(a.X, (long)a.B * a.P * a.Q * a.C * 2L);
-
-  // DMA role of this thread: row t/8 of a BKM-row block, 16-byte slot t%8; LDS slot s of row r holds source piece
-  // s ^ swz(r), and every block starts at a multiple of 32 rows, so the source piece is fixed per thread
-  const int drow = t >> 3, dslot = t & 7;
-  const int dpiece = dslot ^ wg_swz<8>(drow);
-  const unsigned ycol = (unsigned)((n0 + dpiece * 8) * 2), xcol = (unsigned)((c0 + dpiece * 8) * 2);
-  const bool y_ok = n0 + dpiece * 8 < a.N, x_ok = c0 + dpiece * 8 < a.C;
-  // padded position -> pixel index (or -1: padding / outside the tensor)
-  auto pixel_of = [&](int j) -> int {
-    if ((unsigned)j >= (unsigned)a.J) return -1;
-    const int r = fastdiv(j, a.dq), q = j - r * a.Qp;
-    const int b = fastdiv(r, a.dp), p = r - b * (a.P + 1);
-    return (q < a.Q && p < a.P) ? (b * a.P + p) * a.Q + q : -1;
-  };
-  auto issue_y = [&](int step) {  // positions [j0 + BKM step, + BKM) of dY -> tile step % NY (zero past the chunk's end)
-    const int j = j0 + step * BKM + drow;
-    const int m = j < j1 ? pixel_of(j) : -1;
-    const unsigned off = (m >= 0 && y_ok) ? (unsigned)m * (unsigned)(a.ldy * 2) + ycol : ~0u;
-    dma16(rsrc_y, off, 0u, &smem[(step % NY) * TILE_Y + wave * 64 * 8]);
-  };
-  auto issue_x = [&](int u0) {  // ring-relative rows [u0, u0 + BKM): positions j0 - Gpad + u0 + ..
-    const int m = pixel_of(j0 - Gpad + u0 + drow);
-    const unsigned off = (m >= 0 && x_ok) ? (unsigned)m * (unsigned)(a.C * 2) + xcol : ~0u;
-    const int rr = u0 % RING;  // wave-uniform; blocks never straddle the end (RING and u0 are multiples of BKM)
-    dma16(rsrc_x, off, 0u, ring + rr * ROWH + wave * 64 * 8);
-    // block 0 also goes to the mirror.  (One more DMA instruction in the queue on these steps: the counted waits below
-    // then wait for one instruction more than they need to, never for one fewer -- retirement is in order.)
-    if (rr == 0) dma16(rsrc_x, off, 0u, ring + RING * ROWH + wave * 64 * 8);
-  };
-
-  floatx16 acc[2][5];  // [32-row block of the output channels][tap slot: tap = tap0 + slot]
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nb][i][r] = 0.f;
-
-  // transpose-read lane geometry (wgrad.h): 16-lane group gq -> column block (gq & 1) * 16, k half (gq >> 1) * 8; as a
-  // SOURCE lane this lane addresses row lrow = kgrp + (lane & 15) / 4 and the 8-byte chunk (lane & 3) of its column block
-  const int gq = lane >> 4, i16 = lane & 15;
-  const int src_row = i16 >> 2, src_chunk = (i16 & 3) * 4 + (gq & 1) * 16;
-  const int lrow = grp * 32 + (gq >> 1) * 8 + src_row;  // + this wave group's half of the step
-  const unsigned lds0 = lds_addr_of(smem);
-  // A operand (dY tile): row lrow, column nb*32 + src_chunk; the swizzle sees row & 3 = src_row
-  unsigned aA[2];
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb) {
-    const int colA = nb * 32 + src_chunk;
-    aA[nb] = lds0 + (unsigned)((lrow * ROWH + (((colA >> 3) ^ wg_swz<8>(src_row)) * 8) + (colA & 7)) * 2);
-  }
-  // B operand (X ring), tap tp: byte address = ring + rbB[tp] (scalar: first row of the tap's window, advanced per step)
-  // + xoffB[tp] (lane: row lrow, column with the swizzle of (window start + src_row) & 3 -- window starts move in
-  // multiples of 4, so the key is loop invariant per tap) + an immediate for the K sub-step
-  const int colB = wc * 32 + src_chunk;
-  unsigned xoffB[5];
-  int rbB[5];
-#pragma unroll
-  for (int sl = 0; sl < 5; ++sl) {
-    const int tp = tap0 + (sl < ntap ? sl : ntap - 1);  // (the 4-tap half re-reads its last tap in slot 4: no MFMA follows)
-    const int sh = Gpad + (tp / 3 - 1) * a.Qp + (tp % 3 - 1);  // in [0, 2 Gpad] < RING
-    const int key = (sh + src_row) & 3;
-    xoffB[sl] = lds0 + (unsigned)((NY * TILE_Y + lrow * ROWH + ((colB >> 3) ^ (key << 1)) * 8 + (colB & 7)) * 2);
-    rbB[sl] = sh * (ROWH * 2);
-  }
-  const int ring_bytes = RING * ROWH * 2;
-
-  // prologue: the halo rows [0, 2 Gpad), then steps 0 .. D-1 (dY tile + BKM ring rows each), in the order the waits count
-  for (int u0 = 0; u0 < 2 * Gpad; u0 += BKM) issue_x(u0);
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-    if (d < nsteps) {
-      issue_y(d);
-      issue_x(2 * Gpad + BKM * d);
-    }
-
-  for (int s = 0; s < nsteps; ++s) {
-    // steps issued so far: min(nsteps, s + D), at least two DMA instructions each, retired in order: step s has landed
-    // when at most the later ones are outstanding
-    const int ahead = min(nsteps, s + D) - (s + 1);
-    if (D >= 3 && ahead >= 2)
-      wait_vmcnt<4>();
-    else if (D >= 2 && ahead >= 1)
-      wait_vmcnt<2>();
-    else
-      wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();  // step s visible to everyone; everyone is done with step s-1's reads
-    auto issue_step = [&]() {
-      if (s + D < nsteps && (ABL & 1) == 0) {  // into dY tile (s - 1) % NY and the ring rows behind the live + in-flight window
-        issue_y(s + D);
-        issue_x(2 * Gpad + BKM * (s + D));
-      }
-    };
-    if constexpr (DPI < 0) issue_step();
-    const unsigned tyoff = (unsigned)((s % NY) * TILE_Y * 2);
-    // One step = 10 (K sub-step, tap slot) items per wave, each TWO MFMAs (both output-channel blocks) fed by the A
-    // fragments of that sub-step and ONE B fragment read at the tap's row shift.  B fragments travel through a ring of
-    // PD + 1 register buffers: item i + PD is requested right before the MFMAs of item i.
-    constexpr int NKS = 2, ITEMS = NKS * 5, NB = PD + 1;
-    static_assert(2 * PD + 4 <= 15, "lgkmcnt field");
-    TrFrag fa[NKS][2], fb[NB];
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<NKS>([&](auto KS) {
-      constexpr int ks = decltype(KS)::value;
-      static_for<2>([&](auto NBk) {
-        constexpr int nb = decltype(NBk)::value;
-        fa[ks][nb].h[0] = ds_read_tr16_at<(ks * 16) * ROWH * 2>(smem, aA[nb] + tyoff);
-        fa[ks][nb].h[1] = ds_read_tr16_at<(ks * 16 + 4) * ROWH * 2>(smem, aA[nb] + tyoff);
-      });
-    });
-    auto read_b = [&](auto I, TrFrag& f) {
-      constexpr int it = decltype(I)::value, ks = it / 5, sl = it % 5;
-      if constexpr ((ABL & 2) != 0) {
-        f.h[0] = fa[ks][0].h[1];
-        f.h[1] = fa[ks][0].h[0];
-        return;
-      }
-      const unsigned ad = xoffB[sl] + (unsigned)rbB[sl];
-      f.h[0] = ds_read_tr16_at<(ks * 16) * ROWH * 2>(smem, ad);
-      f.h[1] = ds_read_tr16_at<(ks * 16 + 4) * ROWH * 2>(smem, ad);
-    };
-    static_for<(PD < ITEMS ? PD : ITEMS)>([&](auto I) { read_b(I, fb[decltype(I)::value % NB]); });
-    static_for<ITEMS>([&](auto I) {
-      constexpr int it = decltype(I)::value, ks = it / 5, sl = it % 5;
-      if constexpr (it + PD < ITEMS) read_b(StaticIndex<it + PD>{}, fb[(it + PD) % NB]);
-      // LDS reads return in order: once at most the requests issued AFTER item `it` are outstanding (two per item), its
-      // fragment -- and the A fragments, requested before every B fragment -- are in their registers
-      constexpr int later = (ITEMS - 1 - it) < PD ? (ITEMS - 1 - it) : PD;
-      wait_lgkmcnt_for<2 * later>(fb[it % NB]);
-      if constexpr (sl == 0) {
-        wait_lgkmcnt_for<2 * later>(fa[ks][0]);
-        wait_lgkmcnt_for<2 * later>(fa[ks][1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (sl < 4 || tset == 0) {  // wave-uniform: slot 4 of the 4-tap half carries no MFMA
-        if constexpr ((ABL & 4) == 0) {
-          acc[0][sl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][0].v, fb[it % NB].v, acc[0][sl], 0, 0, 0);
-          acc[1][sl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][1].v, fb[it % NB].v, acc[1][sl], 0, 0, 0);
-        } else {
-          asm volatile("" ::"v"(fa[ks][0].v), "v"(fa[ks][1].v), "v"(fb[it % NB].v));
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (it == DPI) {
-        issue_step();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    });
-    // the tap windows move on by one step (scalar)
-#pragma unroll
-    for (int sl = 0; sl < 5; ++sl) {
-      rbB[sl] += BKM * ROWH * 2;
-      rbB[sl] -= rbB[sl] >= ring_bytes ? ring_bytes : 0;
-    }
-  }
-
-  // the two pixel groups hold partial sums of the same tiles: group 1 hands its block-0 tiles to group 0, group 0 hands its
-  // block-1 tiles to group 1 (through LDS, lane-contiguous), then each flushes the block it collected
-  {
-    float* xch = reinterpret_cast<float*>(smem);
-    static_assert((NY * TILE_Y + (RING_MAX + BKM) * ROWH) * 2 >= 4 * 5 * 16 * 64 * 4, "exchange buffer");
-    const int pr = wc + 2 * tset;  // the (column block, tap half) pair this wave shares with its partner of the other group
-    __syncthreads();  // every fragment read of the K loop is done
-    if (grp == 1) {
-#pragma unroll
-      for (int sl = 0; sl < 5; ++sl)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) xch[((pr * 5 + sl) * 16 + r) * 64 + lane] = acc[0][sl][r];
-    }
-    __syncthreads();
-    if (grp == 0) {
-#pragma unroll
-      for (int sl = 0; sl < 5; ++sl)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][sl][r] += xch[((pr * 5 + sl) * 16 + r) * 64 + lane];
-    }
-    __syncthreads();
-    if (grp == 0) {
-#pragma unroll
-      for (int sl = 0; sl < 5; ++sl)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) xch[((pr * 5 + sl) * 16 + r) * 64 + lane] = acc[1][sl][r];
-    }
-    __syncthreads();
-    if (grp == 1) {
-#pragma unroll
-      for (int sl = 0; sl < 5; ++sl)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[1][sl][r] += xch[((pr * 5 + sl) * 16 + r) * 64 + lane];
-    }
-  }
-
-  // partial tile -> workspace slab of this pixel range (plain stores, summed in chunk order by the reduce kernel), or
-  // fp32 atomics straight into dW[n][tap*C + c]
-  const int K9 = 9 * a.C;
-#pragma unroll
-  for (int sl = 0; sl < 5; ++sl) {
-    if (sl >= ntap) continue;  // wave-uniform
-    const int tp = tap0 + sl;
-    const int c = c0 + wc * 32 + (lane & 31);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = n0 + grp * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      const float v = grp == 0 ? acc[0][sl][r] : acc[1][sl][r];
-      if (n < a.N && c < a.C && (ABL & 8) == 0) {
-        if (a.ws)
-          a.ws[((long)ci * a.N + n) * K9 + tp * a.C + c] = v;
-        else
-          unsafeAtomicAdd(a.dW + (long)n * a.ldw + tp * a.C + c, v * a.alpha);
-      }
-    }
-  }
-}
+// (The round-2/3 kernel for plain fp16 tensors -- LDS-DMA three steps ahead, a wave owning BOTH 32-row blocks of the output channels
+// for its taps, 219 registers per lane and 96 KB of LDS -- is gone: equal per launch (106 / 105 / 101 / 108 us at layers 1-4 against
+// 111 / 102 / 98 / 106) and 0.17 ms SLOWER per step, 13.75 vs 13.57 ms (profiles/r04/c10_*), than wgrad_fused_h2_kernel<.., LO = false>
+// below: two 224-register waves per SIMD left no room for a BatchNorm-backward wave of the main stream.  "The fp16 kernel" in the
+// notes below is that kernel: rows of 64 channels = 128 B with 16-byte pieces XOR-swizzled with row & 3, the padded pixel order, and
+// a ring whose first block is mirrored behind its end so that no tap window wraps.)
 
 // ---- fp32x3 form (round 3): the same tap-fused pass for fp32 tensors contracted on the bf16 matrix pipe -------------------
 // wgrad.h's wgrad_x3_kernel is the plain-GEMM form: every one of the nine tap tiles of a channel pair re-reads the pixels
@@ -573,7 +309,7 @@ constexpr int WGF_H2_RING_MAX = 2 * 64 + 2 * 96;
 // a step: per K sub-step 4 A reads, per item 4 B reads + 3 MFMAs -- 1.6 transpose reads per MFMA, as much LDS time as MFMA time.
 // BOTH = true: the fp16 kernel's roles -- wave = (column block) x (pixel half of every step) x (tap half) and BOTH output-channel
 // blocks: a B fragment pair (hi, lo) feeds six MFMAs, 0.93 reads per MFMA; the two pixel halves meet through LDS at the end.
-// LO = false (the fp16 mode's default since round 4, MN_WGF_LIGHT): plain fp16 tensors through the same kernel -- no lo
+// LO = false (the fp16 mode's kernel since round 4): plain fp16 tensors through the same kernel -- no lo
 // planes, one MFMA per item -- i.e. the fp16 tap-fused weight gradient with ~110 instead of 219 registers per lane, so that the
 // BatchNorm kernels of the main stream can share its CUs' register files.
 template <int ABL = 0, int PD = 2, int DPI = 3, bool BOTH = true, bool LO = true>
@@ -878,8 +614,7 @@ inline bool wgrad_fused_h2_applies(const WgradArgs& a) {
 inline void wgrad_fused_reduce(const WgradFusedArgs& a, hipStream_t stream) {
   if (!a.ws) return;
 #ifdef MN_ABLATION_BUILD
-  static const bool skip = getenv("MN_WGF_SKIP_REDUCE") != nullptr;  // timing experiment: what the reduce launches cost a step
-  if (skip) return;
+  if (knobs().wgf_skip_reduce) return;  // timing experiment: what the reduce launches cost a step
 #endif
   const int K9 = 9 * a.C;
   const long quads = (long)a.N * K9 / 4;
@@ -900,8 +635,7 @@ constexpr int WGF_BLOCKS = 512;  // workgroups per launch: two per CU (the regis
 // form: 0 = fp16 tensors, 1 = fp32 tensors on the bf16 pipe (x3), 2 = h2 tensors
 inline void launch_wgrad_fused(const WgradArgs& w, int target_blocks, hipStream_t stream, int form = 0) {
 #ifdef MN_ABLATION_BUILD
-  static const bool skip_all = getenv("MN_ABL_SKIP_WGF") != nullptr;  // timing experiment: the step without the fused weight gradients
-  if (skip_all) return;
+  if (knobs().abl_skip_wgf) return;  // timing experiment: the step without the fused weight gradients
 #endif
   const GatherGeom& g = w.g;
   constexpr int NW = 8, BKM = 8 * NW;  // (the 4-wave form -- two 256-thread workgroups per CU, twice the partial tiles -- is not launched)
@@ -919,16 +653,9 @@ inline void launch_wgrad_fused(const WgradArgs& w, int target_blocks, hipStream_
   a.tiles_c = cdiv(g.C, 64);
   a.Gpad = ((g.Q + 2 + 15) / 16) * 16;
   a.Gpad = ((a.Gpad + 31) / 32) * 32;  // 2 Gpad must be a multiple of the 64-row DMA block
-  constexpr int D = 3;  // DMA steps in flight (the fp32x3 form stages one step ahead through registers)
-  // fp16 tensors: the low-register form of the kernel (134 instead of 219 registers per lane, 64 instead of 96 KB of LDS) is the
-  // default since round 4: equal per launch (111 / 102 / 98 / 106 us against 106 / 105 / 101 / 108 at layers 1-4) and 0.17 ms
-  // faster per step, 13.57 vs 13.75 ms (same-box A/B, two interleaved repeats, profiles/r04/c10_*): two 224-register waves per
-  // SIMD left no room for a BatchNorm-backward wave (122 registers) of the main stream, so the two streams time-sliced the CUs.
-  // MN_WGF_LIGHT=0 restores wgrad_fused_kernel.
-  static const bool light = !(getenv("MN_WGF_LIGHT") && atoi(getenv("MN_WGF_LIGHT")) == 0);
-  if (form == 0 && (light || w.x_h2)) form = 3;  // (the hi halves of an h2 X: the low-register kernel is the one that reads them)
+  if (form == 0) form = 3;  // fp16 tensors (or the hi halves of an h2 X): wgrad_fused_h2_kernel<.., LO = false>
   a.x_h2 = w.x_h2;
-  a.ring = ((form != 0 ? 1 : D) + 1) * BKM + 2 * a.Gpad;
+  a.ring = 2 * BKM + 2 * a.Gpad;  // one DMA step in flight (the fp32x3 form stages one step ahead through registers)
   a.dq = make_fastdiv(a.Qp);
   a.dp = make_fastdiv(g.P + 1);
   a.alpha = w.alpha;
@@ -944,10 +671,6 @@ inline void launch_wgrad_fused(const WgradArgs& w, int target_blocks, hipStream_
   a.chunk = cdiv(cdiv(a.J, chunks), BKM) * BKM;
   a.nchunks = cdiv(a.J, a.chunk);
   if (w.ws && (long)a.nchunks * a.N * 9 * a.C <= w.ws_floats) a.ws = w.ws;
-  static const bool trace = getenv("MN_TRACE_DISPATCH") != nullptr;
-  if (trace)
-    fprintf(stderr, "wgrad_fused<%d waves>: B %d P %d Q %d C %d N %d  chunk %d x %d chunks x %d pairs, ring %d rows, ws %d\n", NW,
-            a.B, a.P, a.Q, a.C, a.N, a.chunk, a.nchunks, pairs, a.ring, a.ws != nullptr);
   const dim3 grid(a.nchunks * pairs), block(NW * 64);
   const bool x3 = form == 1;
   if (form == 3) {  // fp16 tensors through the low-register kernel
@@ -957,7 +680,7 @@ inline void launch_wgrad_fused(const WgradArgs& w, int target_blocks, hipStream_
   }
   if (form == 2) {
 #ifdef MN_ABLATION_BUILD
-    static const int ablh = getenv("MN_WGF_ABLATE") ? atoi(getenv("MN_WGF_ABLATE")) : 0;
+    const int ablh = knobs().wgf_ablate;
     if (ablh == 1) { hipLaunchKernelGGL((wgrad_fused_h2_kernel<1>), grid, block, 0, stream, a); wgrad_fused_reduce(a, stream); return; }
     if (ablh == 4) { hipLaunchKernelGGL((wgrad_fused_h2_kernel<4>), grid, block, 0, stream, a); wgrad_fused_reduce(a, stream); return; }
     if (ablh == 5) { hipLaunchKernelGGL((wgrad_fused_h2_kernel<5>), grid, block, 0, stream, a); wgrad_fused_reduce(a, stream); return; }
@@ -965,19 +688,13 @@ inline void launch_wgrad_fused(const WgradArgs& w, int target_blocks, hipStream_
     // one output-channel block per wave (150 registers) by default: the both-blocks form is 5-10 % faster per launch (224 / 195 /
     // 199 / 210 us against 236 / 220 / 226 / 223 at layers 1-4) and 0.7 ms SLOWER per step, 31.22 vs 30.52 ms: at 240 registers x 2
     // waves per SIMD no BatchNorm wave of the main stream fits beside it (profiles/r04/c9_*)
-    static const int roles = getenv("MN_WGF_H2_ROLES") ? atoi(getenv("MN_WGF_H2_ROLES")) : 0;
-    if (roles == 0)
-      hipLaunchKernelGGL((wgrad_fused_h2_kernel<0, 2, 3, false>), grid, block, 0, stream, a);
-    else if (roles == 2)
-      hipLaunchKernelGGL((wgrad_fused_h2_kernel<0, 1, 3, true>), grid, block, 0, stream, a);
-    else
-      hipLaunchKernelGGL((wgrad_fused_h2_kernel<0, 2, 3, true>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((wgrad_fused_h2_kernel<0, 2, 3, false>), grid, block, 0, stream, a);
     wgrad_fused_reduce(a, stream);
     return;
   }
   if (x3) {
 #ifdef MN_ABLATION_BUILD
-    static const int ablx = getenv("MN_WGF_ABLATE") ? atoi(getenv("MN_WGF_ABLATE")) : 0;
+    const int ablx = knobs().wgf_ablate;
 #define MN_WGFX_ABL(V_)                                                          \
   if (ablx == V_) {                                                              \
     hipLaunchKernelGGL((wgrad_fused_x3_kernel<V_>), grid, block, 0, stream, a); \
@@ -991,23 +708,6 @@ inline void launch_wgrad_fused(const WgradArgs& w, int target_blocks, hipStream_
     wgrad_fused_reduce(a, stream);
     return;
   }
-#ifdef MN_ABLATION_BUILD
-  static const int abl = getenv("MN_WGF_ABLATE") ? atoi(getenv("MN_WGF_ABLATE")) : 0;
-  {
-    switch (abl) {
-      case 1: hipLaunchKernelGGL((wgrad_fused_kernel<D, 1>), grid, block, 0, stream, a); wgrad_fused_reduce(a, stream); return;
-      case 2: hipLaunchKernelGGL((wgrad_fused_kernel<D, 2>), grid, block, 0, stream, a); wgrad_fused_reduce(a, stream); return;
-      case 4: hipLaunchKernelGGL((wgrad_fused_kernel<D, 4>), grid, block, 0, stream, a); wgrad_fused_reduce(a, stream); return;
-      case 8: hipLaunchKernelGGL((wgrad_fused_kernel<D, 8>), grid, block, 0, stream, a); return;
-      case 9: hipLaunchKernelGGL((wgrad_fused_kernel<D, 9>), grid, block, 0, stream, a); return;
-      default: break;
-    }
-  }
-#endif
-  // (B-fragment read-ahead PD = 2 / 4 / 6 and DMA depth 1-3 measured equal in round 2; depth 4 measured slower in round 3:
-  //  104-112 vs 101-110 us per launch, profiles/r03/c10_wgf_depth.txt; PD = 3, D = 3)
-  hipLaunchKernelGGL((wgrad_fused_kernel<D>), grid, block, 0, stream, a);
-  wgrad_fused_reduce(a, stream);
 }
 
 }  // namespace mn

@@ -53,7 +53,7 @@ extern "C" {
  *                 ReLU gate is the exact outcome of the forward pass and BatchNorm's backward sums are taken in fp64 over the forward
  *                 pass's xhat rounded once to fp16 (round 6: a 2-byte record written by the forward apply, csrc/elementwise_h2.h
  *                 rec_pack; round 5 re-read the fp32 conv output; the stem reads an fp16 copy of its conv output unless
- *                 MN_DETERMINISTIC / MN_STEM_BWD=0), so the gradients differ from MN_DTYPE_F16X2's by operand rounding
+ *                 MN_DETERMINISTIC), so the gradients differ from MN_DTYPE_F16X2's by operand rounding
  *                 only: 1.1e-3 relative L2 overall (tools/mixed_budget.py), below the 4.9e-3 by which two fp32 evaluations of
  *                 the reference's step differ through ReLU gate flips.  Loss scale + overflow guard as MN_DTYPE_F16.
  * MN_DTYPE_F16X2Q: (round 5, plans only; experimental) MN_DTYPE_F16X2M whose forward convolutions take BOTH cross terms of a

@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE: convolution parity cases run in a process of their own with a tile configuration forced
-through MN_IGEMM_CONFIG / MN_IGEMM_HALO / MN_WGRAD_FUSED (the library reads such knobs once).  `python forced_config_cases.py emu|hip`.
+through MN_IGEMM_CONFIG / MN_IGEMM_HALO / MN_WGRAD_FUSED (the library reads its knobs at plan creation and at the entry of every
+mn_op_* call, csrc/knobs.h; a process of its own keeps a forced configuration away from the other tests).  `python forced_config_cases.py emu|hip`.
 Configuration 12 = the 12-wave 288x256 tile, which the dispatcher picks by itself only for grids that fill most of
 the chip (layer3 at 192 images); here it runs on small ragged problems against torch fp64."""
 import os

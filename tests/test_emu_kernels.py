@@ -182,7 +182,7 @@ def test_stem_backward_two_launch_form(lib, shape, monkeypatch):
 
 def test_forced_288x256_configuration():
     """the 12-wave 288x256 tile (packed tap masks, joint A/B DMA passes, odd wave-row count) on small ragged problems,
-    in a process of its own because the configuration knob is read once"""
+    in a process of its own so that the forced configuration (read at every operator entry, csrc/knobs.h) reaches no other test"""
     import os
     import subprocess
     import sys

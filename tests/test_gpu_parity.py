@@ -573,7 +573,7 @@ def test_pose_graph_properties_at_eval_set_scale(lib, fc):
 
 def test_forced_288x256_configuration():
     """the 12-wave 288x256 tile on small ragged problems against torch fp64 (tests/forced_config_cases.py), in a
-    process of its own because the configuration knob is read once"""
+    process of its own so that the forced configuration (csrc/knobs.h) reaches no other test"""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -630,7 +630,7 @@ def test_train_and_eval_command_lines(tmp_path):
 
 
 def _run_forced(env, default_path):
-    """kernel variants selected by knobs that are read once run in a process of their own.  default_path=True: the knobs
+    """kernel variants selected by process-wide knobs (csrc/knobs.h) run in a process of their own.  default_path=True: the knobs
     only pin what the product runs anyway (race screens of the default kernels at layer geometries) -- a failure FAILS the
     suite.  default_path=False: an off-by-default variant, parity-checked in the emulator; a failure is reported as xfail
     with the output's tail: the variant is not ready, the product path (the rest of this file) has not lost parity."""
