@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the MapNet training hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            the headline figure only
+  python bench.py --gpus N --steps K --warmup W --full     everything below
+
+A plain run does what `value` needs and nothing else: it builds the workload, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs is given and prints the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`,
+the configuration and the region times; `roofline` is null).  Every other measurement and check of this file takes a run of its own and
+sits behind --full: the event-timed pass for `roofline`, the second timed dtype (`fast_mode`), the oracle leg (`cpu_baseline`, `parity`,
+`meets_tolerance`), `input_feed`, `eval_metric`, with N > 1 the exposed-communication steps, and --all-modes.  The timed steps, their
+inputs and the dumped outputs are the same with and without it; the --no-* options each drop one leg of a --full run.
 
 N > 1 without a launcher: bench.py starts its own N ranks (python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>), one process per GPU; under an
@@ -18,11 +26,11 @@ buckets all-reduced over RCCL while backward continues (weak scaling).
 THE NUMBER OF RECORD (`value`) IS THE ONE INSIDE THE NORTH-STAR TOLERANCE (loss 1e-4, poses 1e-3 against the CPU reference
 path on identical batches): the default --dtype is fp16x2m -- fp16 MFMA arithmetic throughout (fp32 accumulate), every conv
 operand of the FORWARD pass an fp16 PAIR (hi + lo halves split once by the producing kernel, three fp16 MFMAs per product on
-DMA-fed operands), the backward pass one fp16 MFMA per product on exact ReLU gates and BatchNorm statistics.  The same run
-then times plain fp16 storage (`fast_mode`: the dtype BASELINE's configs[2] names; ~1.5x the throughput, does NOT meet the
-tolerance: poses 1.3e-2) with the same code; --all-modes adds the experimental fp16x2q and round 4's fp16x2.
+DMA-fed operands), the backward pass one fp16 MFMA per product on exact ReLU gates and BatchNorm statistics.  With --full the same
+run then times plain fp16 storage (`fast_mode`: the dtype BASELINE's configs[2] names; ~1.5x the throughput, does NOT meet the
+tolerance: poses 1.3e-2) with the same code; --full --all-modes adds the experimental fp16x2q and round 4's fp16x2.
 
-Prints ONE JSON line on rank 0 with
+Prints ONE JSON line on rank 0; with --full it carries
   `value`, `value_at_tolerance`, `dtype_at_tolerance`, `meets_tolerance`   throughput of the timed dtype and whether `parity` is inside the bar;
   `roofline`      all conv MFMA launches of a step, timed with HIP event pairs on the launch stream: `frac` on the reference's
                   algorithmic FLOPs (SURVEY 8d), `pipe_frac` = MFMAs issued / pipe peak, `mfma_busy` from the rocprofv3 SQ counters;
@@ -315,8 +323,8 @@ def region_sizes(steps, repeats):
 
 def timed_mode(args, dtype_name, dev, binding, world, rank, repeats, keep_outputs=False):
     """Build the workload in `dtype_name`, warm up, time exactly --steps steps split into `repeats` regions (barrier +
-    synchronize on both sides, max over ranks), then time the conv MFMA launches of --steps more steps with HIP event
-    pairs.  Returns the record of this mode (every rank), None-valued roofline fields where events are off; with
+    synchronize on both sides, max over ranks), then (--full) time the conv MFMA launches of --steps more steps with HIP
+    event pairs.  Returns the record of this mode (every rank), None-valued roofline fields where events are off; with
     `keep_outputs`, rec["outputs"] holds what the last timed step returned to its caller (loss and poses).  The last timed
     step starts from the initial weights, so what it returns is the same in every run up to rounding."""
     import ctypes as C
@@ -398,7 +406,7 @@ def timed_mode(args, dtype_name, dev, binding, world, rank, repeats, keep_output
         import numpy as np
         rec["outputs"] = {"loss": np.array([l], dtype=np.float64), "poses": poses.detach().float().cpu().numpy()}
     # exposed communication: the compute stream's wait for the gradient all-reduces (geomapnet_amd/dp.py), a few more steps
-    if world > 1 and dev.type == "cuda":
+    if args.full and world > 1 and dev.type == "cuda":
         dp.set_profiling(True)
         for _ in range(min(args.steps, 10)):
             G.step_feedfwd(images, net, True, targets, crit, opt, True)
@@ -413,7 +421,7 @@ def timed_mode(args, dtype_name, dev, binding, world, rank, repeats, keep_output
         rec["comm_exposed_ms"] = round(ex_t.item(), 3)
     # Kernel-level roofline: the conv MFMA launches are timed with HIP event pairs on the launch stream over another run
     # of the SAME K steps (event records serialise the two streams, so this run is not the one `value` comes from).
-    if not args.no_events and not args.emu:  # every rank takes part: with world > 1 each step contains collectives
+    if args.full and not args.no_events and not args.emu:  # every rank takes part: with world > 1 each step contains collectives
         conv_ms, conv_regions = 0.0, 0
         eng.lib.check(eng.lib.set_profiling(plan["handle"], 1))
         sync()
@@ -454,10 +462,15 @@ def main():
                     help="the timed dtype of `value`; default fp16x2m = the mode inside the north-star tolerance")
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=341)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check: the event-timed pass for `roofline`, the "
+                         "second timed dtype, the oracle leg (cpu_baseline, parity, meets_tolerance), input_feed, eval_metric, with "
+                         "N > 1 the exposed-communication steps; without it the run ends with the headline figure.  The --no-* options "
+                         "below each drop one leg of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (cpu_baseline + parity)")
     ap.add_argument("--no-fast-mode", "--no-parity-mode", dest="no_fast_mode", action="store_true",
                     help="skip the second timed pass (plain fp16 storage, `fast_mode`)")
-    ap.add_argument("--all-modes", action="store_true", help="also time fp16x2q (`experimental_mode`) and fp16x2 (`parity_mode_full`)")
+    ap.add_argument("--all-modes", action="store_true", help="(with --full) also time fp16x2q (`experimental_mode`) and fp16x2 (`parity_mode_full`)")
     ap.add_argument("--no-events", action="store_true", help="do not time conv launches with HIP events")
     ap.add_argument("--no-feed", action="store_true", help="skip the PCIe-inclusive legs (input fed from pinned host memory every step)")
     ap.add_argument("--no-eval-metric", action="store_true",
@@ -472,6 +485,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.all_modes and not args.full:
+        ap.error("--all-modes times further dtypes: it needs --full")
 
     launched = "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
@@ -536,7 +551,7 @@ def main():
     # label buys are one measurement; --all-modes: the experimental fp16x2q and round 4's fp16x2 as well
     second = FAST_MODE if args.dtype != FAST_MODE else PARITY_MODE
     sec_rec = pf_rec = px_rec = None
-    if not args.no_fast_mode and not args.emu and args.dtype in (PARITY_MODE, FAST_MODE):
+    if args.full and not args.no_fast_mode and not args.emu and args.dtype in (PARITY_MODE, FAST_MODE):
         sec_rec = timed_mode(args, second, dev, binding, world, rank, min(repeats, 3))
         if args.all_modes:
             px_rec = timed_mode(args, EXPERIMENTAL_MODE, dev, binding, world, rank, min(repeats, 2))
@@ -613,7 +628,7 @@ def main():
         value = images_per_step / (ms_per_step / 1e3)
         out = {"metric": "images/sec MapNet ResNet-34 256x341 T=3 train step", "value": round(value, 2), "unit": "images/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "higher_is_better": True, "full": bool(args.full), "scaling": "weak", "vs_baseline": None,
                "dtype": DT_TEXT[args.dtype], "dtype_mode": args.dtype, "data": "synthetic",
                "config": {"workload": "BASELINE configs[2]: MapNet ResNet-34, %d windows x T=3 = %d images/GPU/step, %dx%d, "
                                       "MapNetCriterion learned beta/gamma, Adam, random-init weights" % (n, n * T, H, W),
@@ -656,7 +671,7 @@ def main():
                                            "which starts from the seeded initial weights" % (args.steps, args.warmup)}
         if args.emu:
             out["data"] = "synthetic (CPU emulator dry-run: NOT a measurement)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 timed = [r_["dtype"] for r_ in (main_rec, sec_rec, px_rec, pf_rec) if r_ is not None]
                 dts = tuple(timed) + ((PARITY_MODE_FULL,) if PARITY_MODE in timed and PARITY_MODE_FULL not in timed else ())
@@ -671,7 +686,7 @@ def main():
                     out["meets_tolerance"] = bool(tol["meets_bar"] and tol["meets_bar_abs"])
             except Exception as e:  # the oracle leg must never hide the GPU number
                 out["cpu_baseline"] = {"error": repr(e)}
-        if world == 1 and not args.no_feed and not args.emu:
+        if args.full and world == 1 and not args.no_feed and not args.emu:
             try:
                 out["input_feed"] = feed_legs(args, args.dtype, dev, binding, ms_per_step)
                 u8 = out["input_feed"]["u8_nhwc"]
@@ -679,7 +694,7 @@ def main():
                 out["value_pcie_inclusive"] = u8["value_pcie_inclusive"]
             except Exception as e:
                 out["input_feed"] = {"error": repr(e)}
-        if world == 1 and not args.no_eval_metric and not args.emu:
+        if args.full and world == 1 and not args.no_eval_metric and not args.emu:
             # BASELINE.json's metric also names "median t/q err": train a LEARNABLE synthetic scene (data.RenderedFrames: the
             # picture is a smooth function of the camera pose) for 1280 steps at 64x85 through the reference's command-line flow
             # (scripts/train.py run -> checkpoint -> scripts/eval.py run) in the timed dtype and in the other mode, identical seeds,

@@ -1,6 +1,7 @@
 """bench.py's launch paths, executed here on the CPU emulator build of the kernels (--emu, gloo):
 `python bench.py --gpus 2` outside any launcher starts its own two ranks (the command the driver uses for N = 1 is the
-same file, same function), and the N = 1 path carries `parity` and `cpu_baseline` from the oracle leg."""
+same file, same function), a plain N = 1 run ends with the headline figure, and with --full the N = 1 path carries `parity`
+and `cpu_baseline` from the oracle leg."""
 import json
 import os
 import subprocess
@@ -36,12 +37,42 @@ def test_bench_self_launches_two_ranks():
 
 @pytest.mark.slow
 def test_bench_single_rank_reports_parity_and_cpu_baseline():
-    d = _run(["--gpus", "1"])
-    assert d["n_gpus"] == 1 and d["config"]["launcher"].startswith("none")
+    d = _run(["--gpus", "1", "--full"])
+    assert d["n_gpus"] == 1 and d["config"]["launcher"].startswith("none") and d["full"] is True
     p = d["parity"]
     assert p["dtype"] == "fp32" and p["loss_rel"] <= 1e-4 and p["pose_abs_max"] <= 1e-3, p
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["cpu"]
+
+
+@pytest.mark.slow
+def test_bench_plain_run_ends_with_the_headline_figure():
+    """without --full: the result line of the timed steps and none of the legs that take runs of their own"""
+    d = _run(["--gpus", "1"])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 1 and d["warmup"] == 0
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "images/s" and d["higher_is_better"] is True
+    assert d["metric"] and d["dtype"] == "f32" and d["roofline"] is None
+    for leg in ("cpu_baseline", "parity", "meets_tolerance", "fast_mode", "parity_mode", "parity_mode_full", "experimental_mode",
+                "input_feed", "eval_metric"):
+        assert leg not in d, leg
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_on_the_device_takes_no_run_of_its_own():
+    """on the device, where --emu drops no leg by itself: a plain run in the default dtype carries no leg that takes a run of its own
+    and no event-timed pass (`roofline` null)"""
+    d = _run(["--gpus", "1"], ["--steps", "2", "--warmup", "1", "--windows", "2", "--height", "64", "--width", "85"])
+    assert d["full"] is False and d["dtype_mode"] == "fp16x2m" and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"] is None and "not a measurement" not in d["data"].lower()
+    for leg in ("cpu_baseline", "parity", "meets_tolerance", "fast_mode", "parity_mode", "parity_mode_full", "experimental_mode",
+                "input_feed", "value_pcie_inclusive", "eval_metric"):
+        assert leg not in d, leg
+
+
+def test_bench_all_modes_needs_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--all-modes"] + TINY, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr
 
 
 @pytest.mark.slow

@@ -17,7 +17,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import geomapnet_amd.engine as E  # noqa: E402
 
-args = types.SimpleNamespace(windows=64, height=256, width=341, warmup=5, steps=30, no_events=True, emu=False)
+args = types.SimpleNamespace(windows=64, height=256, width=341, warmup=5, steps=30, no_events=True, emu=False, full=False)
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
 DT = os.environ.get("DT", "fp16")

@@ -1,11 +1,12 @@
 #!/bin/bash
-# End-of-round check on the GPU box (gpurun -- 'TAG=cNN bash tools/final_check.sh'): the default bench line (fp16x2m = the number of
+# End-of-round check on the GPU box (TAG=cNN bash tools/final_check.sh): the `bench.py --full` line (fp16x2m = the number of
 # record, fp16 beside it), serial kernel stats of both steps, PMC passes (FETCH_SIZE / WRITE_SIZE) and SQ counter passes
 # (tools/sq_counters.sh) of both, the full GPU suite and smoke(); everything lands in gpurun_out/final_$TAG.
-# SKIP_SUITE=1 / SKIP_PMC=1 / SKIP_SQ=1 shorten it.
+# SKIP_SUITE=1 / SKIP_PMC=1 / SKIP_SQ=1 shorten it.  The profiled runs are plain ones (no --full): the --no-* options they still carry,
+# here and in gpu_prof.sh, ab.sh, sq_counters.sh and prof_mode.sh, each drop a leg of a --full run and change nothing in a plain one.
 cd "$GRAFT_REPO_ROOT" || exit 1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final_${TAG:-cur}; mkdir -p $O; export TMPDIR=/tmp
-timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench.err; tail -1 $O/bench_default.json | cut -c1-300
+timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench.err; tail -1 $O/bench_default.json | cut -c1-300
 LEAN="--steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-events --no-fast-mode --no-eval-metric --no-feed"
 for dt in fp16x2m fp16; do
 cd /tmp && MN_WGRAD_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$dt -o r -- python $R/bench.py --dtype $dt $LEAN >> $O/rocprof.log 2>&1

@@ -8,6 +8,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=${TAG:-cur}; R=$GRAFT_REPO_ROOT
 mkdir -p gpurun_out/prof_$TAG; export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the bench line of record carries every leg; the profiled runs below are plain ones
 timeout 900 python bench.py ${BENCH_ARGS} > gpurun_out/prof_$TAG/bench.json 2> gpurun_out/prof_$TAG/bench.err; tail -1 gpurun_out/prof_$TAG/bench.json
 cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o r -- python $R/bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-events --no-parity-mode --no-eval-metric > $R/gpurun_out/prof_$TAG/rocprof.log 2>&1
 cp /tmp/prof_stats/r_kernel_stats.csv $R/gpurun_out/prof_$TAG/kernel_stats.csv
