@@ -61,6 +61,7 @@ _PROTOS = {
     "mn_set_color_jitter": (c_i, [c_void, c_f, c_f, c_f, c_f, C.c_uint64]),
     "mn_set_color_jitter_calls": (c_i, [c_void, C.c_uint32]),
     "mn_forward": (c_i, [c_void, c_void, c_void, c_i, c_void]),
+    "mn_input_grad": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "mn_loss": (c_i, [c_void, c_void, c_void, c_void, c_void]),
     "mn_train_step": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void]),
     "mn_train_forward_loss": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void]),
@@ -108,6 +109,10 @@ _PROTOS = {
     "mn_op_occupy": (c_i, [c_i, c_i, c_f, c_void, c_void, c_i64, c_i, c_void]),
     "mn_op_color_jitter": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, C.POINTER(c_f), C.c_uint64, C.c_uint32,
                                  C.POINTER(c_f), C.POINTER(c_f), c_void]),
+    "mn_op_stem_dgrad": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_f, c_void]),
+    "mn_op_bn_eval_bwd": (c_i, [c_i, c_void, c_void, c_void, c_void, c_i64, c_i, c_void]),
+    "mn_op_saliency": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, c_void]),
+    "mn_op_saliency_work_floats": (c_i64, [c_i]),
 }
 
 SYMBOLS = tuple(_PROTOS)

@@ -21,6 +21,7 @@
 #include "igemm.h"
 #include "dgrad.h"
 #include "halo_pp.h"
+#include "input_grad.h"
 #include "layout.h"
 #include "optim.h"
 #include "pool.h"
@@ -206,6 +207,7 @@ struct PlanBase {
   unsigned long long jit_seed = 0;
   unsigned jit_calls = 0;
   bool jitter_on() const { return jit_range[0] > 0.f || jit_range[1] > 0.f || jit_range[2] > 0.f || jit_range[3] > 0.f; }
+  virtual int input_grad(const void* images, const float* cot, float* gx_out, float* sal_out, float* poses_out, hipStream_t s) = 0;
   virtual int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) = 0;
   virtual int forward_loss(const void* images, const float* targets, float* loss_out, float* poses_out,
                            hipStream_t s) = 0;
@@ -337,6 +339,7 @@ struct Plan : PlanBase {
   int Hl, Wl;  // last feature map
   float *pooled, *feat, *poses, *dposes, *dz, *dpooled, *fcT, *loss_dev, *dropmask;
   float *jit_draws, *jit_partials, *jit_mean;  // ColorJitter: [B][8] draws, [B][kJitterChunks] gray sums, [B] mean gray
+  float *ig_flag, *sal_work;  // input_grad: {1 if the last call's gradient held a non-finite value}, [B][kSalChunks][2] (min, max)
   // BatchNorm sums are accumulated with fp64 atomics straight from the producing kernels (conv epilogue, backward
   // reduction) into ACC_ROWS rows per unit (row = producer block % ACC_ROWS, to spread same-address contention);
   // the consuming apply kernels add the rows in their prologue.  No separate partial-reduction launches.
@@ -480,6 +483,8 @@ struct Plan : PlanBase {
     jit_draws = (float*)A((size_t)B * 8 * 4);  // (last: the buffers above keep their offsets)
     jit_partials = (float*)A((size_t)B * kJitterChunks * 4);
     jit_mean = (float*)A((size_t)B * 4);
+    ig_flag = (float*)A(256);  // (input_grad: behind everything else, as above)
+    sal_work = (float*)A((size_t)B * kSalChunks * 2 * 4);
     return b.cur;
   }
 
@@ -1176,6 +1181,76 @@ struct Plan : PlanBase {
     // last layer1 launches forked a moment ago may still be using it (joined at the end of the stage).
     conv_wgrad(stem, xpad, fork_wgrad(s));
   }
+  // ---- input gradient at inference (mn_input_grad) ---------------------------------------------------------------------
+  // d(sum(cot * poses)) / d(images) in eval mode: the eval forward pass, then the data-gradient chain alone, on the step stream.
+  // Against the training backward pass: BatchNorm is a per-channel scale (running statistics; bn_eval_bwd), there are no weight
+  // gradients, no sums, no optimiser -- parameters, gradient arena, moments, buffers, counters, loss-scale state and acc_region
+  // are not written -- and the chain ends in the stem's data gradient (stem_dgrad), which training never needs.
+  void bn_eval_bwd(Unit& u, const T* g, const T* gate, bool recompute, hipStream_t s) {
+    launch_bn_eval_bwd<T>(g, gate, (const float*)u.coef_f, recompute ? (const float*)(u.coef_f + u.cp.cout) : (const float*)nullptr,
+                          u.gy, u.M, u.cp.cout, s);
+  }
+  int input_grad(const void* images, const float* cot, float* gx_out, float* sal_out, float* poses_out, hipStream_t s) override {
+    if (h2)
+      return fail("mn_input_grad: supported dtypes are MN_DTYPE_F32, MN_DTYPE_F32X3 and MN_DTYPE_F16 (the fp16x2 / fp16x2m / fp16x2q "
+                  "modes have no inference backward pass)");
+    if (jitter_on())
+      return fail("mn_input_grad: attention maps are taken on un-jittered frames; turn ColorJitter off (mn_set_color_jitter with all "
+                  "ranges 0) for this call");
+    if (!images || !gx_out) return fail("mn_input_grad: images and gx_out are required");
+    if (int e = forward_impl(images, poses_out, 0, false, s)) return e;
+    const int F = cfg.feat_dim;
+    hipMemsetAsync(ig_flag, 0, sizeof(float), s);
+    hipLaunchKernelGGL(input_grad_seed_kernel, dim3(cdiv((long)B * 6, 256)), dim3(256), 0, s, cot, dposes, B * 6, 1.f / (6.f * (float)B),
+                       cur_scale);
+    hipLaunchKernelGGL(head_bwd_input_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, s, (const float*)dposes,
+                       (const float*)feat, (const float*)(params + L.xyz_w), (const float*)(params + L.wpqr_w), dz, B, F,
+                       cfg.filter_nans, (const float*)nullptr);
+    GatherGeom gd;
+    gd.B = B; gd.Hi = 1; gd.Wi = 1; gd.C = F; gd.P = 1; gd.Q = 1; gd.R = 1; gd.S = 1; gd.mul_p = 1; gd.mul_q = 1; gd.rsign = 1;
+    gd.ssign = 1; gd.off_h = 0; gd.off_w = 0; gd.div = 1; gd.M = B; gd.N = 512; gd.K = F;
+    Epilogue ep;
+    ep.out = dpooled; ep.ldc = 512; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr;
+    ep.res_gate = nullptr; ep.alpha = 1.f;
+    DenseArgs dd;
+    dd.A = dz; dd.W = fcT; dd.bias = nullptr; dd.C = dpooled; dd.M = B; dd.N = 512; dd.K = F; dd.lda = F; dd.ldw = F; dd.ldc = 512;
+    dd.relu = 0;
+    if (dense_nt_applies(dd))
+      launch_dense_nt(dd, s);
+    else
+      launch_igemm<float>(gd, (const float*)dz, (const float*)fcT, ep, s, (const float*)zero_page);
+    Block& last = blocks.back();
+    hipLaunchKernelGGL((avgpool_bwd_kernel<T>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s, (const float*)dpooled,
+                       last.gout, B, Hl * Wl, 512, (const T*)last.out, 0);
+    for (int i = (int)blocks.size() - 1; i >= 0; --i) {
+      Block& blk = blocks[i];
+      const T* below = i == 0 ? (const T*)nullptr : blk.x;  // (block_backward: the ReLU that produced this block's input)
+      bn_eval_bwd(blk.u2, blk.gout, nullptr, false, s);
+      conv_dgrad(blk.u2, blk.ga1, nullptr, nullptr, s);
+      bn_eval_bwd(blk.u1, blk.ga1, blk.a1, false, s);
+      if (blk.down) {
+        bn_eval_bwd(blk.ud, blk.gout, nullptr, false, s);
+        conv_dgrad(blk.u1, blk.gx, nullptr, nullptr, s, below);
+        conv_dgrad(blk.ud, blk.gx, blk.gx, nullptr, s, below);
+      } else {
+        conv_dgrad(blk.u1, blk.gx, blk.gout, nullptr, s, below);
+      }
+    }
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid((long)B * H0 * W0 * 64 / VEC)), dim3(256), 0, s,
+                       (const unsigned char*)pool_idx, (const T*)gp0, ga0, B, H0, W0, 64, H1, W1);
+    // the fused BatchNorm + ReLU + max-pool pass never stored a0: the stem's gate is recomputed from y and coef_f
+    if (fuse_stem)
+      bn_eval_bwd(stem, ga0, stem.y, true, s);
+    else
+      bn_eval_bwd(stem, ga0, a0, false, s);
+    launch_stem_dgrad<T>(stem.gy, (const float*)(params + stem.cp.w), gx_out, B, H, W, 1.f / cur_scale, ig_flag, s);
+    if (sal_out)
+      launch_saliency(gx_out, input_u8 ? (const float*)nullptr : (const float*)images,
+                      input_u8 ? (const unsigned char*)images : (const unsigned char*)nullptr, input_norm, sal_out, sal_work, B, H, W,
+                      s);
+    return check_launch("input_grad");
+  }
+
   int backward_stage(int stage, hipStream_t s) override {
     if (stage < 0 || stage > 3) return fail("backward_stage: stage must be 0..3");
     if (!cur_targets) return fail("backward_stage: call mn_train_forward_loss first");
@@ -1225,6 +1300,7 @@ struct Plan : PlanBase {
     if (n == "dpooled") return give(dpooled, (long)B * 512, MN_F32);
     if (n == "dropmask") return give(dropmask, (long)B * cfg.feat_dim, MN_F32);
     if (n == "jitter") return give(jit_draws, (long)B * 8, MN_F32);
+    if (n == "input_grad_nonfinite") return give(ig_flag, 1, MN_F32);
     if (n.size() > 2 && n[0] == 'b') {  // "b<block>.<tensor>", blocks numbered 0..15 in network order
       const size_t dot = n.find('.');
       if (dot != std::string::npos) {
@@ -1497,6 +1573,11 @@ extern "C" int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls) {
 extern "C" int mn_forward(mn_handle* h, const void* images, float* poses_out, int training, void* stream) {
   MN_H(h);
   return P.forward(images, poses_out, training, (hipStream_t)stream);
+}
+extern "C" int mn_input_grad(mn_handle* h, const void* images, const float* cot, float* gx_out, float* saliency_out, float* poses_out,
+                             void* stream) {
+  MN_H(h);
+  return P.input_grad(images, cot, gx_out, saliency_out, poses_out, (hipStream_t)stream);
 }
 extern "C" int mn_loss(mn_handle* h, const float* pred, const float* targ, float* loss_out, void* stream) {
   MN_H(h);

@@ -13,6 +13,7 @@
 #include "igemm.h"
 #include "dgrad.h"
 #include "halo_pp.h"
+#include "input_grad.h"
 #include "optim.h"
 #include "pgo.h"
 #include "pool.h"
@@ -445,3 +446,39 @@ extern "C" int mn_op_color_jitter(const unsigned char* in, float* out, float* dr
                           work + (long)B * kJitterChunks, (hipStream_t)stream);
   return check_launch("color_jitter");
 }
+
+extern "C" int mn_op_stem_dgrad(int dtype, const void* gy, const void* w, float* gx, int B, int H, int W, float alpha, void* stream) {
+  begin_op();
+  if (dtype != MN_F32 && dtype != MN_F16) return fail("mn_op_stem_dgrad: dtype must be MN_DTYPE_F32 or MN_DTYPE_F16");
+  if (B < 1 || H < 1 || W < 1 || !gy || !w || !gx) return fail("mn_op_stem_dgrad: B, H, W >= 1 and every pointer required");
+  if ((long)B * H * cdiv(W, kSdTile) >= (1L << 31) - 4096) return fail("mn_op_stem_dgrad: too many output tiles; split the batch");
+  if (dtype == MN_F16)
+    launch_stem_dgrad<half>((const half*)gy, (const float*)w, gx, B, H, W, alpha, nullptr, (hipStream_t)stream);
+  else
+    launch_stem_dgrad<float>((const float*)gy, (const float*)w, gx, B, H, W, alpha, nullptr, (hipStream_t)stream);
+  return check_launch("stem_dgrad");
+}
+
+extern "C" int mn_op_bn_eval_bwd(int dtype, const void* g, const void* gate, const float* scale, void* gy, int64_t M, int C,
+                                 void* stream) {
+  begin_op();
+  if (dtype != MN_F32 && dtype != MN_F16) return fail("mn_op_bn_eval_bwd: dtype must be MN_DTYPE_F32 or MN_DTYPE_F16");
+  const int vec = dtype == MN_F16 ? 8 : 4;
+  if (M < 1 || C < vec || C % vec != 0 || !g || !scale || !gy)
+    return fail("mn_op_bn_eval_bwd: M >= 1, C a multiple of the 16-byte piece (8 halves / 4 floats), g, scale and gy required");
+  if (dtype == MN_F16)
+    launch_bn_eval_bwd<half>((const half*)g, (const half*)gate, scale, nullptr, (half*)gy, (long)M, C, (hipStream_t)stream);
+  else
+    launch_bn_eval_bwd<float>((const float*)g, (const float*)gate, scale, nullptr, (float*)gy, (long)M, C, (hipStream_t)stream);
+  return check_launch("bn_eval_bwd");
+}
+
+extern "C" int mn_op_saliency(const float* gx, const float* x, float* out, float* work, int B, int H, int W, void* stream) {
+  begin_op();
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || !gx || !x || !out || !work)
+    return fail("mn_op_saliency: 1 <= B <= 65535, H, W >= 1 and every pointer required");
+  InputNorm nm{{1.f, 1.f, 1.f}, {0.f, 0.f, 0.f}};
+  launch_saliency(gx, x, nullptr, nm, out, work, B, H, W, (hipStream_t)stream);
+  return check_launch("saliency");
+}
+extern "C" int64_t mn_op_saliency_work_floats(int B) { return (int64_t)B * kSalChunks * 2; }

@@ -363,6 +363,37 @@ class Engine:
         self._jitter_passed(p)
         return out
 
+    INPUT_GRAD_DTYPES = ("fp32", "fp32x3", "fp16")
+
+    def input_grad(self, x, cotangent=None, saliency=False):
+        """d(sum(cotangent * poses)) / d(x) in eval mode (include/mapnet_hip.h mn_input_grad), on the plan `forward` uses for this
+        batch.  x: as `forward`; cotangent: fp32 [B,6], or None for pose.mean().  -> (gx fp32 [B,3,H,W], poses [B,6], maps
+        [B,H,W] or None).  For uint8 input the gradient is with respect to the normalised image.  Training state is untouched."""
+        B = x.shape[0]
+        H, W = self.image_dims(x)
+        dtype = self.dtype or _default_dtype
+        if dtype not in self.INPUT_GRAD_DTYPES:
+            raise MapNetHipError("input_grad: compute dtype %r has no inference backward pass; supported: %s "
+                                 "(set_compute_dtype)" % (dtype, ", ".join(self.INPUT_GRAD_DTYPES)))
+        if self.jitter_active():
+            raise MapNetHipError("input_grad: attention maps are taken on un-jittered frames; call set_color_jitter() with all "
+                                 "ranges 0 first")
+        cot = None
+        if cotangent is not None:
+            if tuple(cotangent.shape) != (B, 6):
+                raise ValueError("input_grad: cotangent must have shape [%d, 6], got %s" % (B, list(cotangent.shape)))
+            cot = cotangent.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        p = self.plan(MODE_POSENET, B, 1, H, W)
+        gx = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
+        poses = torch.empty(B, 6, dtype=torch.float32, device=self.device)
+        maps = torch.empty(B, H, W, dtype=torch.float32, device=self.device) if saliency else None
+        self.lib.check(self.lib.input_grad(p["handle"], ptr(x), ptr(cot), ptr(gx), ptr(maps), ptr(poses), _stream(x)))
+        if p["dtype"] in SCALED_DTYPES and bool(self.debug_tensor(p, "input_grad_nonfinite")[0].item() != 0.0):
+            # not a skipped step: nothing was trained.  The caller lowers the loss scale (set_compute_dtype / Engine.loss_scale)
+            raise MapNetHipError("input_grad: the %s gradient is not finite at loss scale %g; lower the loss scale or use fp32"
+                                 % (p["dtype"], p["cfg"].loss_scale))
+        return gx, poses, maps
+
     def configure_step(self, p, lr, weight_decay, betas, eps, max_grad_norm, learn_beta, learn_gamma, method=(0, 0)):
         h = p["handle"]
         self.lib.check(self.lib.set_optim(h, lr, weight_decay, betas[0], betas[1], eps, max_grad_norm))

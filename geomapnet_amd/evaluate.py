@@ -118,3 +118,39 @@ def evaluate(model, batches, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), cud
         pred_poses, targ_poses = pp, tp
     t_loss, q_loss = pose_errors(pred_poses, targ_poses)
     return summarize(t_loss, q_loss), pred_poses, targ_poses
+
+
+# ---- attention maps: the host side of scripts/plot_activations.py:134-143 of the reference ------------------------------------------
+def _jet(v):
+    """matplotlib's 'jet' colour map on values in [0, 1] -> RGB in [0, 1]; without matplotlib, the piecewise-linear segments jet is
+    defined by (red 0.35-0.66-0.89-1, green 0.125-0.375-0.64-0.91, blue 0-0.11-0.34-0.65), un-quantised"""
+    try:
+        import matplotlib
+        cm = matplotlib.colormaps["jet"] if hasattr(matplotlib, "colormaps") else __import__("matplotlib.cm").cm.get_cmap("jet")
+        return np.asarray(cm(v))[..., :3]
+    except ImportError:
+        r = np.interp(v, [0.0, 0.35, 0.66, 0.89, 1.0], [0.0, 0.0, 1.0, 1.0, 0.5])
+        g = np.interp(v, [0.0, 0.125, 0.375, 0.64, 0.91, 1.0], [0.0, 0.0, 1.0, 1.0, 0.0, 0.0])
+        b = np.interp(v, [0.0, 0.11, 0.34, 0.65, 1.0], [0.5, 1.0, 1.0, 0.0, 0.0])
+        return np.stack([r, g, b], axis=-1)
+
+
+def attention_overlay(frame, amap, mean, std):
+    """One frame of the attention video (plot_activations.py:134-143): jet(amap) * 255 blended 0.5 / 0.5 with the un-normalised
+    frame, clipped to [0, 255], uint8 [H,W,3] in BGR order (what cv2.VideoWriter takes).
+    frame: the normalised fp32 image [3,H,W] the network saw, or the uint8 frame [H,W,3]; amap: [H,W] in [0, 1] (PoseNet.saliency);
+    mean, std: the Normalize statistics (3 values each; unused for a uint8 frame).
+    As in the reference, the colour map's RGB triple is added to the image AFTER the image was flipped to BGR (its line 134 keeps
+    cm_jet's channel order, line 140 flips the image only): in the written BGR frame jet's red end lands in the blue channel."""
+    amap = np.asarray(amap, dtype=np.float64)
+    frame = np.asarray(frame)
+    if frame.dtype == np.uint8:
+        img = frame.astype(np.float64)
+    else:
+        img = frame.astype(np.float64).transpose(1, 2, 0)
+        img = (img * np.asarray(std, dtype=np.float64) + np.asarray(mean, dtype=np.float64)) * 255.0
+    if img.shape[:2] != amap.shape:
+        raise ValueError("attention_overlay: frame %s and map %s differ in size" % (img.shape[:2], amap.shape))
+    act = _jet(np.clip(amap, 0.0, 1.0)) * 255.0
+    out = 0.5 * img[:, :, ::-1] + 0.5 * act
+    return np.clip(out, 0, 255).astype(np.uint8)

@@ -234,6 +234,30 @@ class PoseNet(_ArenaModule):
         # the reference's pinned PyTorch 0.4.1 (F.dropout default training=False at models/posenet.py:68-69)
         return self._engine.forward(x, self.training)
 
+    def _input_grad(self, x, cotangent, saliency):
+        if self.training:
+            raise RuntimeError("input gradients are taken in eval mode (model.eval()): BatchNorm on batch statistics is another "
+                               "function of the input")
+        u8 = self._engine.input_u8 is not None
+        if x.dim() != 4 or (x.shape[-1] if u8 else x.shape[1]) != 3:
+            raise ValueError("expected [N,3,H,W] (or uint8 [N,H,W,3] after set_input_u8)")
+        x = x.detach()
+        if x.device != self._engine.device:
+            raise RuntimeError("input on %s but model on %s" % (x.device, self._engine.device))
+        x = x.contiguous() if u8 else x.float().contiguous()
+        return self._engine.input_grad(x, cotangent, saliency)
+
+    def input_gradient(self, x, cotangent=None):
+        """d(sum(cotangent * poses)) / d(x), fp32 [N,3,H,W]; cotangent None: d(poses.mean()) / d(x), the gradient the reference's
+        scripts/plot_activations.py:117-123 takes.  eval mode only.  uint8 input: with respect to the normalised image."""
+        return self._input_grad(x, cotangent, False)[0]
+
+    def saliency(self, x):
+        """-> (poses [N,6], maps [N,H,W] in [0, 1]): max_c |gradient * image| per pixel, shifted and scaled per image
+        (plot_activations.py:130-133; a constant map comes out all zero).  eval mode only."""
+        _, poses, maps = self._input_grad(x, None, True)
+        return poses, maps
+
 
 class MapNet(nn.Module):
     def __init__(self, mapnet):
@@ -244,6 +268,21 @@ class MapNet(nn.Module):
         s = x.size()
         poses = self.mapnet(x.reshape(-1, *s[2:]))
         return poses.view(s[0], s[1], -1)
+
+    def input_gradient(self, x, cotangent=None):
+        """as PoseNet.input_gradient over [N,T,3,H,W] (cotangent [N,T,6]); the default cotangent is the mean over all N*T*6 poses"""
+        s = x.size()
+        cot = None if cotangent is None else cotangent.reshape(-1, cotangent.shape[-1])
+        return self.mapnet.input_gradient(x.reshape(-1, *s[2:]), cot).view(s[0], s[1], 3, *self._hw(x))
+
+    def saliency(self, x):
+        """-> (poses [N,T,6], maps [N,T,H,W])"""
+        s = x.size()
+        poses, maps = self.mapnet.saliency(x.reshape(-1, *s[2:]))
+        return poses.view(s[0], s[1], -1), maps.view(s[0], s[1], *self._hw(x))
+
+    def _hw(self, x):
+        return self.mapnet._engine.image_dims(x)
 
     def set_input_u8(self, mean=None, std=None):
         self.mapnet.set_input_u8(mean, std)

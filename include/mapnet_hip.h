@@ -196,6 +196,23 @@ int mn_set_color_jitter(mn_handle* h, float brightness, float contrast, float sa
  * replays the draws from 0; data-parallel ranks pass different seeds (scripts/train.py: seed ^ rank << 32). */
 int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls);
 
+/* Attention maps: replaces `data_var = Variable(data, requires_grad=True); pose = model(data_var); pose.mean().backward();
+ * data_var.grad` of scripts/plot_activations.py:117-123, with model.eval() (plot_activations.py:50).  Runs the eval forward pass
+ * and the data-gradient chain alone: BatchNorm on running statistics (a per-channel scale), no weight gradients, no optimiser.
+ * images: as mn_forward (fp32 NCHW, or uint8 NHWC after mn_set_input_u8: the gradient is then taken with respect to the NORMALISED
+ * image).  cot: fp32 [images][6] on the device, the cotangent of the poses, or NULL for 1 / (6 images) everywhere (pose.mean()).
+ * gx_out: fp32 NCHW [images][3][H][W] (the layout of data_var.grad).  saliency_out (or NULL): fp32 [images][H][W], the map of
+ * plot_activations.py:130-133 per image: act = max_c |gx * x|, act -= act.min(), act /= act.max(); a constant act gives an all-zero
+ * map where the reference divides 0 by 0.  poses_out (or NULL): the poses of the forward pass, bit for bit those of mn_forward with
+ * training = 0.  Training state is left as it was: parameters, gradient arena, optimiser moments and step count, BatchNorm buffers,
+ * dropout and jitter pass counts, loss-scale state.  fp16 plans seed the chain with the plan's current loss scale and divide it out
+ * in the last kernel; a non-finite gradient sets the float mn_debug_tensor "input_grad_nonfinite" to 1 (cleared by every call) and is
+ * not a skipped step.  mn_config.filter_nans applies to the rotation head's gradient as in training (models/posenet.py:70-71).
+ * Supported: MN_DTYPE_F32, MN_DTYPE_F32X3, MN_DTYPE_F16; the fp16x2 modes fail with a message.  Fails while ColorJitter is on:
+ * attention maps are taken on un-jittered frames. */
+int mn_input_grad(mn_handle* h, const void* images, const float* cot, float* gx_out, float* saliency_out, float* poses_out,
+                  void* stream);
+
 /* replaces criterion(output, target) (common/train.py:351): loss only, on given predictions */
 int mn_loss(mn_handle* h, const float* pred, const float* targ, float* loss_out, void* stream);
 
@@ -398,6 +415,22 @@ int mn_op_color_jitter(const unsigned char* in, float* out, float* draws, float*
  * ------------------------------------------------------------------------------------------ */
 int mn_op_occupy(int workgroups, int threads, float microseconds, const void* src, void* dst, int64_t bytes, int lds_kb,
                  void* stream);
+
+/* The last link of mn_input_grad's chain: data gradient of conv1 (7x7, stride 2, pad 3, 3 -> 64 channels), i.e.
+ * torch.nn.grad.conv2d_input((B,3,H,W), weight, gy, stride=2, padding=3) -- what autograd runs for data_var.grad at
+ * plot_activations.py:121.  gy: NHWC [B][(H-1)/2+1][(W-1)/2+1][64] of `dtype` (MN_DTYPE_F32 or MN_DTYPE_F16); w: the fp32 OHWI
+ * master [64][7][7][3] (the parameter arena's layout; mn_op_oihw_to_ohwi converts a torch weight), rounded to fp16 inside the
+ * kernel for MN_DTYPE_F16; gx = alpha * gradient, fp32 NCHW [B][3][H][W].  fp32 accumulation on the matrix pipe, no atomics. */
+int mn_op_stem_dgrad(int dtype, const void* gy, const void* w, float* gx, int B, int H, int W, float alpha, void* stream);
+/* BatchNorm backward in eval mode (running statistics: y_bn = y * scale[c] + shift[c], so autograd's gradient is g * scale[c]),
+ * fused with the ReLU that follows the unit: gy = (gate == NULL || gate > 0 ? g : 0) * scale[c].  g, gate, gy: [M][C] of `dtype`
+ * (C a multiple of 8 halves / 4 floats); gate: the unit's ReLU output, or NULL where the incoming gradient is already gated.
+ * scale: fp32 [C] = gamma / sqrt(running_var + eps).  No sums, no d(gamma) / d(beta). */
+int mn_op_bn_eval_bwd(int dtype, const void* g, const void* gate, const float* scale, void* gy, int64_t M, int C, void* stream);
+/* plot_activations.py:130-133 per image: out[b][h][w] = normalised max_c |gx * x| (see mn_input_grad).  gx, x: fp32 NCHW
+ * [B][3][H][W]; out: fp32 [B][H][W]; work: mn_op_saliency_work_floats(B) floats of device memory. */
+int mn_op_saliency(const float* gx, const float* x, float* out, float* work, int B, int H, int W, void* stream);
+int64_t mn_op_saliency_work_floats(int B);
 
 #ifdef __cplusplus
 }
