@@ -81,6 +81,8 @@ _PROTOS = {
     "mn_op_wgrad_ws": (c_i, [c_i, C.POINTER(GatherGeom), c_void, c_i, c_void, c_void, c_i, c_f, c_void, c_i64, c_void, c_void]),
     "mn_op_conv_halo_pp": (c_i, [C.POINTER(GatherGeom), c_void, c_void, c_void, c_i, c_void, c_i, c_i, c_void, c_void, c_void, c_f,
                                  c_i, c_void]),
+    "mn_op_conv_halo_pp_h2gates": (c_i, [C.POINTER(GatherGeom), c_void, c_void, c_void, c_i, c_void, c_i, c_i, c_void, c_void, c_void,
+                                         c_f, c_i, c_void]),
     "mn_op_conv_halo_h2": (c_i, [C.POINTER(GatherGeom), c_void, c_void, c_void, c_i, c_void, c_i, c_void]),
     "mn_op_conv_dgrad": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_i,
                                c_void, c_void]),
@@ -91,6 +93,8 @@ _PROTOS = {
     "mn_op_head_wgrad": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void, c_i, c_i, c_f, c_i, c_void]),
     "mn_op_stem_bwd": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_i, c_void, c_void, c_void,
                              c_void, c_void, c_i, c_i, c_i, c_i, c_f, c_void]),
+    "mn_op_stem_bwd_pregated": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_i, c_void, c_void,
+                                      c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_f, c_void]),
     "mn_op_oihw_to_ohwi": (c_i, [c_void, c_void, c_i, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_criterion": (c_i, [c_i, c_i, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_f, c_void]),
     "mn_op_calc_vos": (c_i, [c_void, c_i, c_i, c_void, c_void, c_void, c_void]),
@@ -104,6 +108,14 @@ _PROTOS = {
                                  c_void, c_f, c_f, c_void, c_void]),
     "mn_op_bn_bwd": (c_i, [c_i, c_void, c_void, c_void, c_i64, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
                            c_void, c_f, c_void]),
+    "mn_op_bn_train_fwd_h2": (c_i, [c_void, c_i64, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_i, c_void, c_void,
+                                    c_f, c_f, c_void, c_void]),
+    "mn_op_bn_bwd_rows": (c_i, [c_i, c_void, c_void, c_void, c_i64, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
+                                c_void, c_void, c_i, c_f, c_void]),
+    "mn_op_bn_relu_maxpool_h2": (c_i, [c_void, c_void, c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_void]),
+    "mn_op_avgpool_fwd_h2": (c_i, [c_void, c_void, c_i, c_i, c_i, c_void]),
+    "mn_op_avgpool_bwd": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_void]),
+    "mn_op_widen_f16": (c_i, [c_void, c_void, c_i64, c_void]),
     "mn_op_maxpool_fwd": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_maxpool_bwd": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_occupy": (c_i, [c_i, c_i, c_f, c_void, c_void, c_i64, c_i, c_void]),

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "criterion.h"
 #include "elementwise.h"
+#include "elementwise_h2.h"
 #include "head.h"
 #include "jitter.h"
 #include "knobs.h"
@@ -94,19 +95,30 @@ extern "C" int mn_op_igemm(int dtype, const mn_gather_geom* gg, const void* A, c
   return check_launch("igemm");
 }
 
-extern "C" int mn_op_conv_halo_pp(const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
-                                 int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate,
-                                 float alpha, int wgs, void* stream) {
+static int op_conv_halo_pp(const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
+                           int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate, float alpha, int wgs,
+                           bool gate_h2, void* stream) {
   begin_op();
   GatherGeom g = to_geom(gg);
   if (int e = check_geom(g, MN_F16)) return e;
   Epilogue ep;
   ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = relu; ep.res = res; ep.res_gate = res_gate;
   ep.out_gate = out_gate; ep.alpha = alpha; ep.stats_accum = stats_accum; ep.stats_rows = stats_rows;
+  ep.gate_h2 = gate_h2;
   if (!conv_halo_pp_applies(g, ep))
     return fail("conv_halo_pp: fp16 3x3 stride-1 same-size convolutions of 64 -> 64 channels only (stats_rows > 0 with stats_accum)");
   launch_conv_halo_pp(g, (const half*)A, (const half*)Bw, ep, (hipStream_t)stream, wgs);
   return check_launch("conv_halo_pp");
+}
+extern "C" int mn_op_conv_halo_pp(const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
+                                 int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate,
+                                 float alpha, int wgs, void* stream) {
+  return op_conv_halo_pp(gg, A, Bw, out, ldc, stats_accum, stats_rows, relu, res, res_gate, out_gate, alpha, wgs, false, stream);
+}
+extern "C" int mn_op_conv_halo_pp_h2gates(const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc,
+                                          double* stats_accum, int stats_rows, int relu, const void* res, const void* res_gate,
+                                          const void* out_gate, float alpha, int wgs, void* stream) {
+  return op_conv_halo_pp(gg, A, Bw, out, ldc, stats_accum, stats_rows, relu, res, res_gate, out_gate, alpha, wgs, true, stream);
 }
 
 static int op_wgrad(int dtype, const mn_gather_geom* gg, const void* dY, int ldy, const void* X, float* dW, int ldw,
@@ -144,13 +156,18 @@ static int op_wgrad(int dtype, const mn_gather_geom* gg, const void* dY, int ldy
   a.ws = ws;
   a.ws_floats = ws_floats;
   a.g = to_geom(gg);
-  int vec = dtype == MN_F16 ? 8 : 4;
+  if (dtype < MN_DTYPE_F32 || dtype > MN_DTYPE_F16X2M)
+    return fail("wgrad: dtype must be MN_DTYPE_F32, _F16, _F32X3, _F16X2 or _F16X2M");
+  const bool mixed = dtype == MN_DTYPE_F16X2M;  // the fp16 kernels: dY plain fp16, X the hi halves of an h2 tensor
+  int vec = dtype == MN_F16 || mixed ? 8 : 4;
   if (a.g.C % vec != 0 || a.g.N % vec != 0) return fail("wgrad: channel counts must be multiples of the piece");
   if (dtype == MN_DTYPE_F16X2 && (a.g.C % 32 != 0 || ldy % 32 != 0)) return fail("wgrad: h2 operands need channel counts % 32 == 0");
+  if (mixed && a.g.C % 32 != 0) return fail("wgrad: an h2 X operand needs C % 32 == 0");
   a.dY = dY; a.ldy = ldy; a.X = X; a.dW = dW; a.ldw = ldw; a.colmap = colmap; a.alpha = alpha; a.rows_per_split = 0;
   if (dtype == MN_DTYPE_F32X3) a.g.mma = MMA_BF16X3;  // fp32 tensors, bf16 matrix pipe with split operands
   if (dtype == MN_DTYPE_F16X2) a.g.mma = MMA_H2;      // h2 tensors (dY, X), fp32 dW
-  if (dtype == MN_F16 || dtype == MN_DTYPE_F16X2)
+  a.x_h2 = mixed;
+  if (dtype == MN_F16 || dtype == MN_DTYPE_F16X2 || mixed)
     launch_wgrad<half>(a, target_blocks, (hipStream_t)stream, zero_page);
   else
     launch_wgrad<float>(a, target_blocks, (hipStream_t)stream);
@@ -202,10 +219,10 @@ extern "C" int mn_op_head_wgrad(const float* dposes, const float* feat, float* d
   return check_launch("head_wgrad");
 }
 
-extern "C" int mn_op_stem_bwd(const void* y, const unsigned char* idx, const void* gp, const float* gamma, const float* beta,
-                              const float* mean, const float* invstd, const void* xpad, float* dW, int ldw, const int32_t* colmap,
+static int op_stem_bwd(const void* y, const unsigned char* idx, const void* gp, const float* gamma, const float* beta,
+                       const float* mean, const float* invstd, const void* xpad, float* dW, int ldw, const int32_t* colmap,
                               float* dgamma, float* dbeta, float* coef_scratch, double* accum_scratch, int B, int H, int W, int Wp,
-                              float alpha, void* stream) {
+                              float alpha, int pre_gated, void* stream) {
   begin_op();
   if (Wp % 2 != 0 || Wp < W + 7) return fail("stem_bwd: Wp must be even and >= W + 7");
   hipStream_t s = (hipStream_t)stream;
@@ -214,12 +231,28 @@ extern "C" int mn_op_stem_bwd(const void* y, const unsigned char* idx, const voi
   a.y = (const half*)y; a.idx = idx; a.gp = (const half*)gp; a.gamma = gamma; a.beta = beta; a.coef = coef_scratch; a.mean = mean;
   a.invstd = invstd; a.accum = accum_scratch; a.accum_rows = 1; a.xpad = (const half*)xpad; a.dW = dW; a.colmap = colmap;
   a.ldw = ldw; a.alpha = alpha;
+  a.pre_gated = pre_gated;
   hipMemsetAsync(accum_scratch, 0, 2 * 64 * sizeof(double), s);
   launch_stem_bn_reduce(a, B, H, W, Wp, s);
   hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(64 / kBnFinalizeChannels), dim3(256), 0, s, (const double*)accum_scratch, (double)((long)B * H0 * W0), gamma,
                      mean, invstd, dgamma, dbeta, alpha, beta, coef_scratch, 64, 1);
   launch_stem_wgrad(a, B, H, W, Wp, s);
   return check_launch("stem_bwd");
+}
+
+extern "C" int mn_op_stem_bwd(const void* y, const unsigned char* idx, const void* gp, const float* gamma, const float* beta,
+                              const float* mean, const float* invstd, const void* xpad, float* dW, int ldw, const int32_t* colmap,
+                              float* dgamma, float* dbeta, float* coef_scratch, double* accum_scratch, int B, int H, int W, int Wp,
+                              float alpha, void* stream) {
+  return op_stem_bwd(y, idx, gp, gamma, beta, mean, invstd, xpad, dW, ldw, colmap, dgamma, dbeta, coef_scratch, accum_scratch, B, H,
+                     W, Wp, alpha, 0, stream);
+}
+extern "C" int mn_op_stem_bwd_pregated(const void* y, const unsigned char* idx, const void* gp, const float* gamma, const float* beta,
+                                       const float* mean, const float* invstd, const void* xpad, float* dW, int ldw,
+                                       const int32_t* colmap, float* dgamma, float* dbeta, float* coef_scratch,
+                                       double* accum_scratch, int B, int H, int W, int Wp, float alpha, void* stream) {
+  return op_stem_bwd(y, idx, gp, gamma, beta, mean, invstd, xpad, dW, ldw, colmap, dgamma, dbeta, coef_scratch, accum_scratch, B, H,
+                     W, Wp, alpha, 1, stream);
 }
 
 extern "C" int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, int H, int W, int to_ohwi, void* stream) {
@@ -258,21 +291,26 @@ extern "C" int mn_op_conv_dgrad(int dtype, int B, int Hin, int Win, int Cin, int
   if (k < 1 || k > 5 || pad < 0 || pad >= k) return fail("conv_dgrad: kernel / padding out of range");
   if (!zero_page) return fail("conv_dgrad: zero_page (>= 16 zero bytes of device memory) is required");
   const int Hout = (Hin + 2 * pad - k) / stride + 1, Wout = (Win + 2 * pad - k) / stride + 1;
-  const int vec = dtype == MN_F16 ? 8 : 4;
+  if (dtype < MN_DTYPE_F32 || dtype > MN_DTYPE_F16X2M)
+    return fail("conv_dgrad: dtype must be MN_DTYPE_F32, _F16, _F32X3, _F16X2 or _F16X2M");
+  const bool mixed = dtype == MN_DTYPE_F16X2M;  // the fp16 kernels with h2 gates (hi halves read)
+  const int vec = dtype == MN_F16 || mixed ? 8 : 4;
   if (dtype == MN_DTYPE_F16X2 && (Cin % 32 != 0 || Cout % 32 != 0)) return fail("conv_dgrad: h2 operands need channel counts % 32 == 0");
+  if (mixed && (res_gate || out_gate) && Cin % 32 != 0) return fail("conv_dgrad: h2 gates need Cin % 32 == 0");
   DgradGeom d = make_dgrad_geom(B, Hin, Win, Cin, Cout, k, stride, pad, Hout, Wout, vec);
-  if (int e = check_geom(d.full, dtype)) return e;
+  if (int e = check_geom(d.full, mixed ? MN_F16 : dtype)) return e;
   if (Cin % vec != 0) return fail("conv_dgrad: Cin must be a multiple of the 16-byte piece");
   Epilogue ep;
   ep.out = gx; ep.ldc = Cin; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = res; ep.res_gate = res_gate;
   ep.out_gate = out_gate; ep.alpha = 1.f;
+  ep.gate_h2 = mixed;
   if (dtype == MN_DTYPE_F32X3) {
     d.full.mma = MMA_BF16X3;
     for (int i = 0; i < d.n_pc; ++i) d.pc[i].g.mma = MMA_BF16X3;
   }
   if (dtype == MN_DTYPE_F16X2)  // gy, wd, res_gate, out_gate h2; gx, res fp32
     launch_conv_dgrad<half>(d, (const half*)gy, (const half*)wd, ep, (hipStream_t)stream, (const half*)zero_page, parity != 0, true);
-  else if (dtype == MN_F16)
+  else if (dtype == MN_F16 || mixed)
     launch_conv_dgrad<half>(d, (const half*)gy, (const half*)wd, ep, (hipStream_t)stream, (const half*)zero_page, parity != 0);
   else
     launch_conv_dgrad<float>(d, (const float*)gy, (const float*)wd, ep, (hipStream_t)stream, (const float*)zero_page,
@@ -325,12 +363,12 @@ extern "C" int mn_op_optim(int method, int nesterov, float* p, const float* g, f
   return check_launch("optim");
 }
 
+// standalone operator: statistics by a direct reduction (the network path takes them from the conv epilogue instead), then the
+// finalize launch.  accum: [2][C] doubles + [2][C] floats of (scale, shift) after it; returns the coefficients.
 template <typename T>
-static int bn_train_fwd_t(const void* y, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
-                          float* running_var, float* mean, float* invstd, const void* res, int relu, void* out, float eps,
-                          float momentum, double* accum, hipStream_t s) {
-  // standalone operator: statistics by a direct reduction (the network path takes them from the
-  // conv epilogue instead).  accum: [2][C] doubles + [2][C] floats of scale/shift after it.
+static const float* bn_stats_finalize(const void* y, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
+                                      float* running_var, float* mean, float* invstd, float eps, float momentum, double* accum,
+                                      hipStream_t s) {
   hipMemsetAsync(accum, 0, 2 * C * sizeof(double), s);
   int rows_per_block = 256;
   hipLaunchKernelGGL((bn_fwd_stats_kernel<T>), dim3(cdiv(M, rows_per_block)), dim3(256), 0, s, (const T*)y, (long)M, C,
@@ -338,10 +376,18 @@ static int bn_train_fwd_t(const void* y, int64_t M, int C, const float* gamma, c
   BnParams p;
   p.gamma = gamma; p.beta = beta; p.running_mean = running_mean; p.running_var = running_var;
   p.num_batches_tracked = nullptr; p.mean = mean; p.invstd = invstd; p.eps = eps; p.momentum = momentum;
-  long np = M * C / ElemTraits<T>::VEC;
   float* coef = reinterpret_cast<float*>(accum + 2 * C);  // [2][C] floats behind the accumulators
   hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, (const double*)accum, (double)M, p, 1, coef, C, 1);
-  hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(ew_grid(np)), dim3(256), 0, s, (const T*)y, (const float*)coef, (const T*)res,
+  return coef;
+}
+
+template <typename T>
+static int bn_train_fwd_t(const void* y, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, float* mean, float* invstd, const void* res, int relu, void* out, float eps,
+                          float momentum, double* accum, hipStream_t s) {
+  const float* coef = bn_stats_finalize<T>(y, M, C, gamma, beta, running_mean, running_var, mean, invstd, eps, momentum, accum, s);
+  long np = M * C / ElemTraits<T>::VEC;
+  hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(ew_grid(np)), dim3(256), 0, s, (const T*)y, coef, (const T*)res,
                      (T*)out, np, C, relu);
   return check_launch("bn_train_fwd");
 }
@@ -355,11 +401,19 @@ static int check_bn_channels(int dtype, int C) {
     return fail("bn: C must be a power of two times the 16-byte piece (8 halves / 4 floats), at most 512");
   return 0;
 }
+// the h2 / record kernels (elementwise_h2.h): a thread owns 8 channels, rows hold whole 32-channel groups
+static int check_bn_channels_h2(int C) {
+  if (C < 32 || C > 512 || (C & (C - 1)) != 0) return fail("bn: the h2 / record kernels need C = 32, 64, 128, 256 or 512");
+  return 0;
+}
 
 extern "C" int mn_op_bn_train_fwd(int dtype, const void* y, int64_t M, int C, const float* gamma, const float* beta,
                                   float* running_mean, float* running_var, float* mean, float* invstd, const void* res,
                                   int relu, void* out, float eps, float momentum, double* accum_scratch, void* stream) {
   begin_op();
+  if (dtype != MN_F32 && dtype != MN_F16 && dtype != MN_DTYPE_F32X3)
+    return fail("bn_train_fwd: dtype must be MN_DTYPE_F32 (or _F32X3: the same fp32 tensors) or MN_DTYPE_F16; the h2 form is "
+                "mn_op_bn_train_fwd_h2");
   if (int e = check_bn_channels(dtype, C)) return e;
   if (dtype == MN_F16)
     return bn_train_fwd_t<half>(y, M, C, gamma, beta, running_mean, running_var, mean, invstd, res, relu, out, eps,
@@ -368,28 +422,111 @@ extern "C" int mn_op_bn_train_fwd(int dtype, const void* y, int64_t M, int C, co
                                momentum, accum_scratch, (hipStream_t)stream);
 }
 
+extern "C" int mn_op_bn_train_fwd_h2(const float* y, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
+                                     float* running_var, float* mean, float* invstd, const void* res, int relu, void* out,
+                                     void* rec, float eps, float momentum, double* accum_scratch, void* stream) {
+  begin_op();
+  if (int e = check_bn_channels_h2(C)) return e;
+  if (M < 1 || !y || !gamma || !beta || !running_mean || !running_var || !out || !mean || !invstd || !accum_scratch)
+    return fail("bn_train_fwd_h2: M >= 1 and every pointer but res and rec required");
+  hipStream_t s = (hipStream_t)stream;
+  const float* coef = bn_stats_finalize<float>(y, M, C, gamma, beta, running_mean, running_var, mean, invstd, eps, momentum,
+                                               accum_scratch, s);
+  const long ni = M * C / 8;
+  hipLaunchKernelGGL(bn_apply_h2_kernel, dim3(ew_grid(ni)), dim3(256), 0, s, y, coef, (const half*)res, (half*)out, ni, C, relu, 0,
+                     (half*)rec, (const float*)mean, (const float*)invstd);
+  return check_launch("bn_train_fwd_h2");
+}
+
 template <typename T>
-static int bn_bwd_t(const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma, const float* mean,
-                    const float* invstd, float* dgamma, float* dbeta, void* gy, float* coef, double* accum,
-                    float grad_unscale, hipStream_t s) {
-  if (!coef) return fail("bn_bwd: coef_scratch (3*C floats) is required");
+static int bn_bwd_t(const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma, const float* beta,
+                    const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy, float* coef, double* accum,
+                    int accum_rows, float grad_unscale, hipStream_t s) {
   launch_bn_bwd<T>((const T*)g, (const T*)gate, (const T*)y, (long)M, C, gamma, mean, invstd, dgamma, dbeta, (T*)gy, accum,
-                   coef, grad_unscale, s);
-  hipMemsetAsync(accum, 0, 2 * C * sizeof(double), s);  // hand the scratch back zeroed
+                   coef, grad_unscale, s, beta, PoolGradSrc(), accum_rows);
+  return 0;
+}
+
+static int op_bn_bwd(int dtype, const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma,
+                     const float* beta, const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy,
+                     float* coef, double* accum, int accum_rows, float grad_unscale, void* stream) {
+  begin_op();
+  hipStream_t s = (hipStream_t)stream;
+  const bool h2 = dtype == MN_DTYPE_F16X2, rec = dtype == MN_DTYPE_F16X2M;
+  if (dtype != MN_F32 && dtype != MN_F16 && dtype != MN_DTYPE_F32X3 && !h2 && !rec)
+    return fail("bn_bwd: dtype must be MN_DTYPE_F32 (or _F32X3: the same fp32 tensors), _F16, _F16X2 or _F16X2M");
+  if (int e = (h2 || rec) ? check_bn_channels_h2(C) : check_bn_channels(dtype, C)) return e;
+  if (accum_rows < 1 || accum_rows > 4096) return fail("bn_bwd: 1 <= accum_rows <= 4096");
+  if (!coef) return fail("bn_bwd: coef_scratch (3*C floats, 4*C with a self gate) is required");
+  if ((h2 || rec) && (M < 1 || !g || !y || !gy || !gamma || !mean || !invstd || !dgamma || !dbeta || !accum))
+    return fail("bn_bwd: M >= 1 and every pointer but gate and beta required");
+  if (h2 && gate) return fail("bn_bwd: MN_DTYPE_F16X2 takes the gradient as stored (already gated) or recomputes the unit's own ReLU (beta)");
+  const long an = (long)accum_rows * 2 * C;
+  hipMemsetAsync(accum, 0, an * sizeof(double), s);
+  if (rec)  // g fp16, y = the 2-byte record of the forward apply; gate selects use_gate (the gate bits are the record's)
+    launch_bn_bwd_rec((const half*)g, (const half*)y, (long)M, C, gamma, mean, invstd, dgamma, dbeta, (half*)gy, accum, coef,
+                      grad_unscale, s, gate != nullptr, accum_rows);
+  else if (h2)  // g, y fp32; gy h2; beta: the unit's own ReLU, recomputed from y
+    launch_bn_bwd_h2((const float*)g, (const float*)y, (long)M, C, gamma, mean, invstd, dgamma, dbeta, (half*)gy, accum, coef,
+                     grad_unscale, s, beta, accum_rows);
+  else if (dtype == MN_F16)
+    bn_bwd_t<half>(g, gate, y, M, C, gamma, beta, mean, invstd, dgamma, dbeta, gy, coef, accum, accum_rows, grad_unscale, s);
+  else
+    bn_bwd_t<float>(g, gate, y, M, C, gamma, beta, mean, invstd, dgamma, dbeta, gy, coef, accum, accum_rows, grad_unscale, s);
+  hipMemsetAsync(accum, 0, an * sizeof(double), s);  // hand the scratch back zeroed
   return check_launch("bn_bwd");
 }
 
 extern "C" int mn_op_bn_bwd(int dtype, const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma,
                             const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy,
                             float* coef_scratch, double* accum_scratch, float grad_unscale, void* stream) {
+  return op_bn_bwd(dtype, g, gate, y, M, C, gamma, nullptr, mean, invstd, dgamma, dbeta, gy, coef_scratch, accum_scratch, 1,
+                   grad_unscale, stream);
+}
+extern "C" int mn_op_bn_bwd_rows(int dtype, const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma,
+                                 const float* beta, const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy,
+                                 float* coef_scratch, double* accum_scratch, int accum_rows, float grad_unscale, void* stream) {
+  return op_bn_bwd(dtype, g, gate, y, M, C, gamma, beta, mean, invstd, dgamma, dbeta, gy, coef_scratch, accum_scratch, accum_rows,
+                   grad_unscale, stream);
+}
+
+extern "C" int mn_op_bn_relu_maxpool_h2(const float* y, const float* coef, void* out, unsigned char* idx, void* y16, int B, int H,
+                                        int W, int C, void* stream) {
   begin_op();
-  if (int e = check_bn_channels(dtype, C)) return e;
-  hipMemsetAsync(accum_scratch, 0, 2 * C * sizeof(double), (hipStream_t)stream);
-  if (dtype == MN_F16)
-    return bn_bwd_t<half>(g, gate, y, M, C, gamma, mean, invstd, dgamma, dbeta, gy, coef_scratch, accum_scratch,
-                          grad_unscale, (hipStream_t)stream);
-  return bn_bwd_t<float>(g, gate, y, M, C, gamma, mean, invstd, dgamma, dbeta, gy, coef_scratch, accum_scratch,
-                         grad_unscale, (hipStream_t)stream);
+  if (int e = check_bn_channels_h2(C)) return e;
+  if (B < 1 || H < 1 || W < 1 || !y || !coef || !out) return fail("bn_relu_maxpool_h2: B, H, W >= 1, y, coef and out required");
+  const int Po = (H + 2 - 3) / 2 + 1, Qo = (W + 2 - 3) / 2 + 1;
+  hipLaunchKernelGGL(bn_relu_maxpool_h2_kernel, dim3(ew_grid((long)B * Po * Qo * C / 8)), dim3(256), 0, (hipStream_t)stream, y, coef,
+                     (half*)out, idx, B, H, W, C, Po, Qo, (half*)y16, 0);
+  return check_launch("bn_relu_maxpool_h2");
+}
+
+extern "C" int mn_op_avgpool_fwd_h2(const void* in, float* out, int B, int HW, int C, void* stream) {
+  begin_op();
+  if (B < 1 || HW < 1 || C < 32 || C % 32 != 0 || !in || !out) return fail("avgpool_fwd_h2: B, HW >= 1, C a multiple of 32, in and out required");
+  hipLaunchKernelGGL(avgpool_fwd_h2_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, (hipStream_t)stream, (const half*)in, out, B, HW,
+                     C, 0);
+  return check_launch("avgpool_fwd_h2");
+}
+
+extern "C" int mn_op_avgpool_bwd(int dtype, const float* gp, void* g, const void* gate, int B, int HW, int C, void* stream) {
+  begin_op();
+  if (dtype != MN_DTYPE_F16X2 && dtype != MN_DTYPE_F16X2M)
+    return fail("avgpool_bwd: dtype must be MN_DTYPE_F16X2 (fp32 gradient) or MN_DTYPE_F16X2M (fp16 gradient); the gate is an h2 tensor");
+  if (B < 1 || HW < 1 || C < 32 || C % 32 != 0 || !gp || !g) return fail("avgpool_bwd: B, HW >= 1, C a multiple of 32, gp and g required");
+  const dim3 grid(ew_grid((long)B * HW * C));
+  if (dtype == MN_DTYPE_F16X2M)
+    hipLaunchKernelGGL((avgpool_bwd_kernel<half>), grid, dim3(256), 0, (hipStream_t)stream, gp, (half*)g, B, HW, C, (const half*)gate, 1);
+  else
+    hipLaunchKernelGGL(avgpool_bwd_h2_kernel, grid, dim3(256), 0, (hipStream_t)stream, gp, (float*)g, B, HW, C, (const half*)gate);
+  return check_launch("avgpool_bwd");
+}
+
+extern "C" int mn_op_widen_f16(const void* in, float* out, int64_t n, void* stream) {
+  begin_op();
+  if (n < 8 || n % 8 != 0 || !in || !out) return fail("widen_f16: n a positive multiple of 8, in and out required");
+  hipLaunchKernelGGL(widen_f16_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const half*)in, out, (long)(n / 8));
+  return check_launch("widen_f16");
 }
 
 extern "C" int mn_op_maxpool_fwd(int dtype, const void* in, void* out, unsigned char* idx, int B, int H, int W, int C,

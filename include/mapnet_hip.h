@@ -45,7 +45,7 @@ extern "C" {
  *                 v_mfma_f32_32x32x16_f16 per product on operands that reach LDS by DMA, with no conversion in their K loops.
  *                 Gradients are kept inside fp16's range by the loss scale + overflow guard of MN_DTYPE_F16.  Operator entry
  *                 points: dtype 3 = A / Bw / dY / X / gates h2, out / res / dW fp32.
- * MN_DTYPE_F16X2M: (round 5, plans only) the forward pass of MN_DTYPE_F16X2 bit for bit -- the loss and the predicted poses of a
+ * MN_DTYPE_F16X2M: (round 5) the forward pass of MN_DTYPE_F16X2 bit for bit -- the loss and the predicted poses of a
  *                 step ARE that mode's, i.e. inside the north-star tolerance -- and a backward pass on the MN_DTYPE_F16 kernels:
  *                 one MFMA per product on single fp16 operands (d(conv output), data gradients and the data-gradient weight copy
  *                 are plain fp16; the weight gradients' X operand and the ReLU gates read plain fp16 copies of the activations
@@ -55,7 +55,12 @@ extern "C" {
  *                 rec_pack; round 5 re-read the fp32 conv output; the stem reads an fp16 copy of its conv output unless
  *                 MN_DETERMINISTIC), so the gradients differ from MN_DTYPE_F16X2's by operand rounding
  *                 only: 1.1e-3 relative L2 overall (tools/mixed_budget.py), below the 4.9e-3 by which two fp32 evaluations of
- *                 the reference's step differ through ReLU gate flips.  Loss scale + overflow guard as MN_DTYPE_F16.
+ *                 the reference's step differ through ReLU gate flips.  Loss scale + overflow guard as MN_DTYPE_F16.  Operator entry
+ *                 points: dtype 4 selects the backward kernel variants only this mode launches -- mn_op_wgrad / mn_op_wgrad_ws: dY plain
+ *                 fp16, X an h2 tensor of which the hi halves are read, dW fp32 (C % 32 == 0); mn_op_conv_dgrad: gy, wd, gx, res plain fp16,
+ *                 res_gate / out_gate h2 tensors (mn_op_conv_halo_pp_h2gates for the layer1 kernel); mn_op_bn_bwd / mn_op_bn_bwd_rows: g, gy
+ *                 fp16, y = the 2-byte record; mn_op_avgpool_bwd: fp16 gradient, h2 gate.  Its forward kernels are MN_DTYPE_F16X2's
+ *                 (mn_op_igemm dtype 3, mn_op_bn_train_fwd_h2, mn_op_bn_relu_maxpool_h2, mn_op_avgpool_fwd_h2); no entry takes 4 otherwise.
  * MN_DTYPE_F16X2Q: (round 5, plans only; experimental) MN_DTYPE_F16X2M whose forward convolutions take BOTH cross terms of a
  *                 split-operand product from fp8 (e4m3) copies with fixed exponents on gfx950's block-scaled MFMA
  *                 (v_mfma_scale_f32_32x32x64_f8f6f4, twice the fp16 rate): conv-consumed tensors are "h2q" -- fp16 hi halves where
@@ -308,6 +313,11 @@ int mn_op_wgrad_ws(int dtype, const mn_gather_geom* g, const void* dY, int ldy, 
 int mn_op_conv_halo_pp(const mn_gather_geom* g, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
                        int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate, float alpha,
                        int wgs, void* stream);
+/* mn_op_conv_halo_pp with res_gate / out_gate given as h2 tensors [B][H][W][64] of which the hi halves are read (Epilogue::gate_h2:
+ * the data gradients of layer1 in the fp16x2m mode); every other operand as above. */
+int mn_op_conv_halo_pp_h2gates(const mn_gather_geom* g, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
+                               int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate, float alpha,
+                               int wgs, void* stream);
 /* 3x3 stride-1 same-size FORWARD convolution of 64 -> 64 channel h2 tensors (ResNet layer1 in the fp16x2 / fp16x2m modes) with the
  * weights held in registers (csrc/halo_h2.h): one persistent 4-wave workgroup per CU, a wave keeps the hi and lo halves of its 32
  * output channels' weights as MFMA operands for the whole launch and only the input halo of an 8 x 16-pixel tile passes through LDS.
@@ -355,6 +365,13 @@ int mn_op_stem_bwd(const void* y, const unsigned char* idx, const void* gp, cons
                    const float* mean, const float* invstd, const void* xpad, float* dW, int ldw, const int32_t* colmap,
                    float* dgamma, float* dbeta, float* coef_scratch, double* accum_scratch, int B, int H, int W, int Wp,
                    float alpha, void* stream);
+/* The same two launches with gp ALREADY multiplied by the stem's ReLU gate (StemBwdArgs::pre_gated, the fp16x2m mode: layer1.0's data
+ * gradient gates gp with the pooled activation): the gate is not recomputed from y, which may then be an fp16 copy of an fp32 conv
+ * output whose recomputed sign could differ near zero. */
+int mn_op_stem_bwd_pregated(const void* y, const unsigned char* idx, const void* gp, const float* gamma, const float* beta,
+                            const float* mean, const float* invstd, const void* xpad, float* dW, int ldw, const int32_t* colmap,
+                            float* dgamma, float* dbeta, float* coef_scratch, double* accum_scratch, int B, int H, int W, int Wp,
+                            float alpha, void* stream);
 /* conv weight layout helpers: OIHW fp32 <-> OHWI fp32 */
 int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, int H, int W, int to_ohwi, void* stream);
 
@@ -393,6 +410,39 @@ int mn_op_bn_train_fwd(int dtype, const void* y, int64_t M, int C, const float* 
 int mn_op_bn_bwd(int dtype, const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma,
                  const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy, float* coef_scratch,
                  double* accum_scratch, float grad_unscale, void* stream);
+/* mn_op_bn_train_fwd: dtype MN_DTYPE_F32 (MN_DTYPE_F32X3: the same fp32 tensors) or MN_DTYPE_F16; any other dtype fails.
+ * mn_op_bn_bwd operands by dtype (any other dtype fails):
+ *   MN_DTYPE_F32 / _F32X3 / _F16: g, gate (or NULL), y, gy of that type.
+ *   MN_DTYPE_F16X2:  g, y fp32; gy an h2 tensor; gate must be NULL (block-output gradients arrive already gated);
+ *                    C = 32 .. 512, a power of two (launch_bn_bwd_h2).
+ *   MN_DTYPE_F16X2M: g, gy plain fp16; `y` is the 2-byte backward RECORD [M][C] written by mn_op_bn_train_fwd_h2 (fp16 xhat with the
+ *                    ReLU outcome in the lowest mantissa bit); gate NULL / non-NULL = ignore / apply the record's gate bits (the
+ *                    pointer is not read); C as above (launch_bn_bwd_rec).
+ * mn_op_bn_bwd_rows: the same operator with the two parameters the plan has: accum_rows >= 1 rows of accumulators, over which the
+ * reduction's workgroups spread their atomics (accum_scratch = accum_rows * 2*C doubles, handed back zeroed), and beta (or NULL):
+ * with beta the gradient is taken with respect to relu(bn(y)) of THIS BatchNorm and the gate is recomputed from y (gate is not
+ * read; coef_scratch = 4*C floats) -- the only gate of MN_DTYPE_F16X2; ignored by MN_DTYPE_F16X2M, whose gate is the record's. */
+int mn_op_bn_bwd_rows(int dtype, const void* g, const void* gate, const void* y, int64_t M, int C, const float* gamma,
+                      const float* beta, const float* mean, const float* invstd, float* dgamma, float* dbeta, void* gy,
+                      float* coef_scratch, double* accum_scratch, int accum_rows, float grad_unscale, void* stream);
+/* Training-mode BatchNorm forward of the fp16x2 / fp16x2m modes (statistics, finalize, bn_apply_h2_kernel): y fp32 [M][C] in,
+ * out = [relu](bn(y) [+ res]) as an h2 tensor, res an optional h2 tensor; rec (or NULL): the backward record of this BatchNorm, fp16
+ * [M][C] = fp16(xhat) rounded to nearest with the lowest mantissa bit replaced by the gate -- relu(bn(y)) > 0 for relu without res, 1 in
+ * every other variant.  mean / invstd / running statistics / accum_scratch as mn_op_bn_train_fwd.  C = 32 .. 512, a power of two. */
+int mn_op_bn_train_fwd_h2(const float* y, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, float* mean, float* invstd, const void* res, int relu, void* out, void* rec, float eps,
+                          float momentum, double* accum_scratch, void* stream);
+/* Stem of the fp16x2 / fp16x2m modes: out = maxpool3x3/2/1(relu(y * coef[c] + coef[C + c])) in one pass (bn_relu_maxpool_h2_kernel).
+ * y: fp32 [B][H][W][C]; coef: fp32 [2][C] (scale, shift); out: h2 [B][Po][Qo][C]; idx (or NULL): winning taps as mn_op_maxpool_fwd;
+ * y16 (or NULL): plain fp16 copy of y, [B][H][W][C], every element written once.  C = 32 .. 512, a power of two. */
+int mn_op_bn_relu_maxpool_h2(const float* y, const float* coef, void* out, unsigned char* idx, void* y16, int B, int H, int W, int C,
+                             void* stream);
+/* Global average pool of an h2 activation [B][HW][C] -> fp32 [B][C], and its backward: g[b][p][c] = gp[b][c] / HW, zeroed where the
+ * hi half of the h2 tensor `gate` (or NULL: no gate) is <= 0.  dtype MN_DTYPE_F16X2: g fp32; MN_DTYPE_F16X2M: g plain fp16.  C % 32 == 0. */
+int mn_op_avgpool_fwd_h2(const void* in, float* out, int B, int HW, int C, void* stream);
+int mn_op_avgpool_bwd(int dtype, const float* gp, void* g, const void* gate, int B, int HW, int C, void* stream);
+/* out[i] = (float) in[i] for n fp16 values, n a multiple of 8 (the fp16x2m mode's pooled stem gradient for the fp32 stem chain) */
+int mn_op_widen_f16(const void* in, float* out, int64_t n, void* stream);
 /* 3x3/2 pad 1 max-pool; idx (optional, uint8 per output element) records the winning tap for the backward */
 int mn_op_maxpool_fwd(int dtype, const void* in, void* out, unsigned char* idx, int B, int H, int W, int C,
                       void* stream);

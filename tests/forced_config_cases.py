@@ -32,6 +32,8 @@ def main(backend):
                     checks.check_conv_wgrad(lib, dev, 1, *shape, target_blocks=1024, seed=2 + rep)
                     if os.environ.get("MN_WGRAD_FUSED") == "1":  # the fp32x3 form of the fused kernel (wgrad_fused_x3_kernel)
                         checks.check_conv_wgrad(lib, dev, 2, *shape, seed=12 + rep, ws=True)
+            if os.environ.get("MN_WGRAD_FUSED") == "1":  # one pass of the form the default mode (fp16x2m) launches: the hi halves of an h2 X
+                checks.check_conv_wgrad(lib, dev, 4, 24, 64, 86, 64, 64, 3, 1, 1, seed=30, ws=True)
         print("forced-config cases ok")
         return
     if os.environ.get("MN_H2_CASES") == "1":
@@ -69,6 +71,10 @@ def main(backend):
         for mode in ("plain", "out_gate", "res_gate"):
             checks.check_conv_dgrad_op(lib, dev, 1, 2, 12, 43, 128, 128, 3, 1, 1, parity=1, mode=mode)
         checks.check_conv_dgrad_op(lib, dev, 1, 9, 8, 11, 512, 512, 3, 1, 1, parity=1, mode="res_gate")
+        # the same epilogues with the gates as h2 tensors (dtype 4, Epilogue::gate_h2: what the default mode, fp16x2m, launches)
+        for mode in ("out_gate", "res_gate"):
+            checks.check_conv_dgrad_op(lib, dev, 4, 2, 12, 43, 128, 128, 3, 1, 1, parity=1, mode=mode)
+        checks.check_conv_dgrad_op(lib, dev, 4, 9, 8, 11, 512, 512, 3, 1, 1, parity=1, mode="res_gate")
         if backend != "emu":  # layer2 / layer4 geometries at a size that fills the chip, repeated (race screen)
             for rep in range(3):
                 checks.check_conv_fwd(lib, dev, 1, 48, 32, 43, 128, 128, 3, 1, 1, seed=rep)
@@ -86,6 +92,10 @@ def main(backend):
         for mode in ("plain", "out_gate", "res_gate"):
             checks.check_conv_dgrad_op(lib, dev, 1, 3, 16, 22, 256, 256, 3, 1, 1, parity=1, mode=mode)
         checks.check_conv_dgrad_op(lib, dev, 1, 5, 8, 11, 256, 128, 3, 1, 1, parity=1, mode="out_gate")
+        # the same epilogues with the gates as h2 tensors (dtype 4, Epilogue::gate_h2)
+        for mode in ("out_gate", "res_gate"):
+            checks.check_conv_dgrad_op(lib, dev, 4, 3, 16, 22, 256, 256, 3, 1, 1, parity=1, mode=mode)
+        checks.check_conv_dgrad_op(lib, dev, 4, 5, 8, 11, 256, 128, 3, 1, 1, parity=1, mode="out_gate")
         if backend != "emu":  # layer3 / layer4 geometries with hundreds of concurrent workgroups, repeated (race screen)
             for rep in range(3):
                 checks.check_conv_fwd(lib, dev, 1, 96, 16, 22, 256, 256, 3, 1, 1, seed=rep)

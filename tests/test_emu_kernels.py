@@ -46,7 +46,7 @@ def test_conv_data_gradient(lib, dtype, shape):
     checks.check_conv_dgrad(lib, DEV, dtype, *shape)
 
 
-@pytest.mark.parametrize("dtype", [0, 1, 2, 3])
+@pytest.mark.parametrize("dtype", [0, 1, 2, 3, 4])
 @pytest.mark.parametrize("shape,blocks", [
     ((2, 9, 11, 64, 64, 3, 1, 1), 8),
     ((3, 9, 11, 64, 128, 3, 2, 1), 8),
@@ -116,7 +116,7 @@ def test_pose_graph_properties(lib):
     checks.check_pgo_properties(lib, DEV, W=24, N=7, fc=True)
 
 
-@pytest.mark.parametrize("dtype", [0, 1, 2, 3])
+@pytest.mark.parametrize("dtype", [0, 1, 2, 3, 4])
 @pytest.mark.parametrize("shape,mode", [
     ((2, 8, 11, 64, 128, 3, 2, 1), "plain"),      # odd width: the parity classes have 6 and 5 columns
     ((2, 9, 10, 64, 128, 3, 2, 1), "out_gate"),   # odd height
@@ -155,12 +155,12 @@ def test_conv_data_gradient_parity_random_geometry(lib, case):
 
 @pytest.mark.parametrize("shape", [(2, 9, 11, 64, 64, 3, 1, 1), (3, 20, 22, 128, 64, 3, 1, 1), (40, 3, 5, 64, 128, 3, 1, 1),
                                    (2, 6, 7, 72, 80, 3, 1, 1), (2, 8, 11, 256, 256, 3, 1, 1)])
-@pytest.mark.parametrize("dtype", [1, 2, 3])
+@pytest.mark.parametrize("dtype", [1, 2, 3, 4])
 def test_fused_weight_gradient_through_workspace(lib, dtype, shape):
     """wgrad_fused.h (fp16 kernel; fp32x3 kernel: fp32 tensors split into bf16 halves at the LDS write) with partial tiles
     stored to a (NaN-filled) workspace and added up by the reduce kernel, as the plan runs it; bit-identical between two
-    launches when a single reduction group covers the columns"""
-    if dtype == 3 and shape[3] % 32:  # h2 tensors hold whole 32-channel groups: 96 / 160 channels = 1.5 / 2.5 tiles of 64
+    launches when a single reduction group covers the columns.  dtype 4 (the fp16x2m mode): plain fp16 dY against the hi halves of an h2 X"""
+    if dtype in (3, 4) and shape[3] % 32:  # h2 tensors hold whole 32-channel groups: 96 / 160 channels = 1.5 / 2.5 tiles of 64
         shape = shape[:3] + (96, 160) + shape[5:]
     checks.check_conv_wgrad(lib, DEV, dtype, *shape, ws=True)
 
@@ -265,3 +265,73 @@ def test_occupancy_stand_in_streams_its_bytes_and_lasts_its_time(lib):
 def test_layer1_h2_convolution_with_the_weights_in_registers(lib, shape):
     """halo_h2.h (round 6): ragged tiles, several tiles per workgroup (the emulated chip has 4 CUs), statistics"""
     checks.check_conv_halo_h2(lib, DEV, *shape)
+
+
+# ---- the kernel variants only the fp16x2 / fp16x2m plans launch, as operators (DESIGN.md section 8.1 lists kernel -> entry -> check) ----
+BN_H2_SHAPES = [
+    (77, 128),          # fewer rows than one reduction block, tail lanes masked
+    (300, 64),          # 3 reduction blocks of 128 rows, the last ragged; 32 row lanes
+    (130, 512),         # 4 row lanes, 64 pieces per row: the top of the apply kernels' coefficient table
+    (2 * 64 * 86, 64),  # layer1 geometry
+]
+
+
+@pytest.mark.parametrize("M,C", BN_H2_SHAPES)
+def test_batchnorm_h2_forward_and_record_backward(lib, M, C):
+    """bn_apply_h2_kernel with and without the 2-byte record (rec_pack), then bn_bwd_reduce_rec_kernel / bn_bwd_apply_rec_kernel on
+    the records it wrote"""
+    fwd = checks.check_bn_h2_forward(lib, DEV, M, C)
+    checks.check_bn_rec_backward(lib, DEV, fwd)
+
+
+@pytest.mark.parametrize("self_gate,rows", [(False, 1), (True, 1), (True, 4)])
+@pytest.mark.parametrize("M,C", BN_H2_SHAPES)
+def test_batchnorm_h2_backward(lib, M, C, self_gate, rows):
+    """bn_bwd_apply_h2_kernel / launch_bn_bwd_h2: fp32 gradient and conv output in, h2 d(conv output) out"""
+    checks.check_bn_h2_backward(lib, DEV, M, C, self_gate, rows)
+
+
+def test_operator_entries_reject_dtypes_and_channel_counts_they_do_not_have(lib):
+    checks.check_bn_dtype_errors(lib, DEV)
+
+
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("shape", [(2, 8, 11), (2, 9, 10), (1, 33, 70)])
+def test_stem_batchnorm_relu_maxpool_h2(lib, shape, exact):
+    """bn_relu_maxpool_h2_kernel: pooled h2 value, argmax routing, the fp16 copy y16"""
+    checks.check_stem_pool_h2(lib, DEV, *shape, exact=exact)
+
+
+@pytest.mark.parametrize("shape", [(3, 88, 512), (2, 7, 512)])
+def test_average_pool_h2(lib, shape):
+    """avgpool_fwd_h2_kernel, avgpool_bwd_h2_kernel, avgpool_bwd_kernel<half> with an h2 gate"""
+    checks.check_avgpool_h2(lib, DEV, *shape)
+
+
+def test_widen_f16(lib):
+    checks.check_widen_f16(lib, DEV, 8 * 777)
+
+
+@pytest.mark.parametrize("wgs", [0, 7])
+@pytest.mark.parametrize("mode", ["out_gate", "res_gate"])
+@pytest.mark.parametrize("shape", [(3, 9, 11), (1, 33, 70), (2, 64, 86)])
+def test_conv_halo_pp_data_gradient_with_h2_gates(lib, shape, mode, wgs):
+    """halo_pp.h with Epilogue::gate_h2 (mn_op_conv_halo_pp_h2gates): layer1's data gradients in the fp16x2m mode"""
+    B, H, W = shape
+    checks.check_conv_halo(lib, DEV, B, H, W, Cout=64, dgrad=True, mode=mode, seed=H * 100 + W + 1, pp_wgs=wgs, gate_h2=True)
+
+
+@pytest.mark.parametrize("mode", ["out_gate", "res_gate"])
+@pytest.mark.parametrize("shape", [(2, 12, 43, 128, 128, 3, 1, 1), (2, 7, 47, 384, 128, 3, 1, 1)])
+def test_conv_data_gradient_h2_gates_through_the_chunk_resident_kernel(lib, shape, mode):
+    """igemm_halo.h with Epilogue::gate_h2: 3x3 stride-1 data gradients whose Cin is a multiple of 128 go to the chunk-resident-A
+    kernel by default (its other tile shapes: the forced-configuration cases)"""
+    checks.check_conv_dgrad_op(lib, DEV, 4, *shape, parity=1, mode=mode)
+
+
+@pytest.mark.parametrize("shape", [(1, 20, 27), (2, 33, 70)])
+def test_stem_backward_two_launch_form_pre_gated(lib, shape, monkeypatch):
+    """csrc/stem_bwd.h with StemBwdArgs::pre_gated (mn_op_stem_bwd_pregated): the pooled gradient arrives gated, by a mask the
+    conv output's sign does not reproduce"""
+    monkeypatch.setenv("MN_STEM_WGS", "3")
+    checks.check_stem_bwd(lib, DEV, *shape, pre_gated=True)
