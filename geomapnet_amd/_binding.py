@@ -60,6 +60,8 @@ _PROTOS = {
     "mn_set_input_u8": (c_i, [c_void, c_i, C.POINTER(c_f), C.POINTER(c_f)]),
     "mn_set_color_jitter": (c_i, [c_void, c_f, c_f, c_f, c_f, C.c_uint64]),
     "mn_set_color_jitter_calls": (c_i, [c_void, C.c_uint32]),
+    "mn_input_resize_bytes": (c_i64, [C.POINTER(Config), c_i, c_i]),
+    "mn_set_input_resize": (c_i, [c_void, c_i, c_i, c_void, c_i64]),
     "mn_forward": (c_i, [c_void, c_void, c_void, c_i, c_void]),
     "mn_input_grad": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "mn_loss": (c_i, [c_void, c_void, c_void, c_void, c_void]),
@@ -121,6 +123,9 @@ _PROTOS = {
     "mn_op_occupy": (c_i, [c_i, c_i, c_f, c_void, c_void, c_i64, c_i, c_void]),
     "mn_op_color_jitter": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, C.POINTER(c_f), C.c_uint64, C.c_uint32,
                                  C.POINTER(c_f), C.POINTER(c_f), c_void]),
+    "mn_op_resize_u8": (c_i, [c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_i, c_void]),
+    "mn_op_resize_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
+    "mn_op_resize_tile": (c_i, [c_i, c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
     "mn_op_stem_dgrad": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_f, c_void]),
     "mn_op_bn_eval_bwd": (c_i, [c_i, c_void, c_void, c_void, c_void, c_i64, c_i, c_void]),
     "mn_op_saliency": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, c_void]),

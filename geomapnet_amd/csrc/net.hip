@@ -16,6 +16,7 @@
 #include "elementwise_h2.h"
 #include "head.h"
 #include "jitter.h"
+#include "resize.h"
 #include "knobs.h"
 #include "dense.h"
 #include "igemm.h"
@@ -207,6 +208,11 @@ struct PlanBase {
   unsigned long long jit_seed = 0;
   unsigned jit_calls = 0;
   bool jitter_on() const { return jit_range[0] > 0.f || jit_range[1] > 0.f || jit_range[2] > 0.f || jit_range[3] > 0.f; }
+  // Resize on uint8 input (mn_set_input_resize): `images` are source frames, resampled into the caller's buffer rs_frames at the
+  // head of a pass; everything downstream reads rs_frames where it read `images`.  Off: nothing is launched for it
+  bool resize_on = false;
+  ResizeGeom rs_geom;
+  unsigned char* rs_frames = nullptr;
   virtual int input_grad(const void* images, const float* cot, float* gx_out, float* sal_out, float* poses_out, hipStream_t s) = 0;
   virtual int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) = 0;
   virtual int forward_loss(const void* images, const float* targets, float* loss_out, float* poses_out,
@@ -797,6 +803,10 @@ struct Plan : PlanBase {
     if (jitter_on() && !input_u8)
       return fail("forward: ColorJitter (mn_set_color_jitter) needs uint8 input (mn_set_input_u8): fp32 frames arrive already "
                   "normalised, and ColorJitter must come before Normalize");
+    if (resize_on && !input_u8)
+      return fail("forward: Resize (mn_set_input_resize) needs uint8 input (mn_set_input_u8): fp32 frames arrive already "
+                  "normalised, and Resize must come before Normalize");
+    if (resize_on && !images) return fail("forward: images are required");
     // work the stem and layer1 do not depend on goes to the side stream: the repack of the later layers'
     // weights and optim.learner.zero_grad(); joined before layer2
     const bool dirty = weights_dirty;
@@ -809,6 +819,10 @@ struct Plan : PlanBase {
     }
     // (fp16x2m: the stem's fp16 backward kernels read an fp16 image of the input -- written by the same launch)
     half* const x16 = stem_bwd_f16() && training ? xpad16 : (half*)nullptr;
+    if (resize_on) {  // Resize first: the conversion below reads the resized frames
+      launch_resize_u8((const unsigned char*)images, rs_frames, rs_geom, s);
+      images = rs_frames;
+    }
     if (input_u8 && jitter_on())
       launch_jitter_input((const unsigned char*)images, x16, s);
     else if (input_u8)
@@ -1199,6 +1213,7 @@ struct Plan : PlanBase {
                   "ranges 0) for this call");
     if (!images || !gx_out) return fail("mn_input_grad: images and gx_out are required");
     if (int e = forward_impl(images, poses_out, 0, false, s)) return e;
+    if (resize_on) images = rs_frames;  // the x of the saliency map: the frames the network saw
     const int F = cfg.feat_dim;
     hipMemsetAsync(ig_flag, 0, sizeof(float), s);
     hipLaunchKernelGGL(input_grad_seed_kernel, dim3(cdiv((long)B * 6, 256)), dim3(256), 0, s, cot, dposes, B * 6, 1.f / (6.f * (float)B),
@@ -1563,6 +1578,43 @@ extern "C" int mn_set_color_jitter(mn_handle* h, float brightness, float contras
   for (int k = 0; k < 4; ++k) P.jit_range[k] = v[k];
   P.jit_seed = seed;
   P.jit_calls = 0;
+  return 0;
+}
+static int resize_images(const mn_config* c) {
+  return c->windows * (c->mode == MN_MODE_POSENET ? 1 : (c->mode == MN_MODE_MAPNET ? c->T : 2 * c->T));
+}
+extern "C" int64_t mn_input_resize_bytes(const mn_config* cfg, int src_h, int src_w) {
+  if (validate(cfg)) return -1;
+  if (src_h < 1 || src_w < 1) {
+    fail("mn_input_resize_bytes: the source size must be positive");
+    return -1;
+  }
+  return resize_frames_bytes(resize_images(cfg), cfg->H, cfg->W) + resize_table_bytes(src_h, src_w, cfg->H, cfg->W);
+}
+extern "C" int mn_set_input_resize(mn_handle* h, int src_h, int src_w, void* work, int64_t work_bytes) {
+  MN_H(h);
+  if (src_h == 0 && src_w == 0) {
+    P.resize_on = false;
+    P.rs_frames = nullptr;
+    return 0;
+  }
+  if (src_h < 1 || src_w < 1) return fail("mn_set_input_resize: the source size must be positive (0, 0 turns the resize off)");
+  if (!work) return fail("mn_set_input_resize: work (device memory of mn_input_resize_bytes) is required");
+  if (((uintptr_t)work & 3) != 0) return fail("mn_set_input_resize: work must be 4-byte aligned");
+  const int64_t frames = resize_frames_bytes(resize_images(&P.cfg), P.cfg.H, P.cfg.W);
+  const int64_t need = frames + resize_table_bytes(src_h, src_w, P.cfg.H, P.cfg.W);
+  if (work_bytes < need)
+    return fail("mn_set_input_resize: work holds " + std::to_string((long long)work_bytes) + " bytes, mn_input_resize_bytes asks for " +
+                std::to_string((long long)need));
+  const ResizePlan rp = resize_plan(resize_images(&P.cfg), src_h, src_w, P.cfg.H, P.cfg.W, (int*)((unsigned char*)work + frames));
+  if (!rp.error.empty()) return fail("mn_set_input_resize: " + rp.error);
+  // passes in flight may still read the tables of an earlier setting in the same buffer
+  if (hipDeviceSynchronize() != hipSuccess) return check_launch("set_input_resize");
+  if (hipMemcpy((unsigned char*)work + frames, rp.tables.data(), rp.tables.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    return check_launch("set_input_resize");
+  P.rs_geom = rp.g;
+  P.rs_frames = (unsigned char*)work;
+  P.resize_on = true;
   return 0;
 }
 extern "C" int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls) {

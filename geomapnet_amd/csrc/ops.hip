@@ -19,6 +19,7 @@
 #include "pgo.h"
 #include "pool.h"
 #include "rehearsal.h"
+#include "resize.h"
 #include "stem.h"
 #include "stem_bwd.h"
 #include "wgrad.h"
@@ -582,6 +583,64 @@ extern "C" int mn_op_color_jitter(const unsigned char* in, float* out, float* dr
   launch_u8_jitter<float>(in, out, B, H, W, H + 6, W + 6, nm, nullptr, jitter_params(ranges, seed, call), draws, work,
                           work + (long)B * kJitterChunks, (hipStream_t)stream);
   return check_launch("color_jitter");
+}
+
+// The tables of one mn_op_resize_u8 call travel through a pinned buffer of the calling thread (kept for the thread's life), so
+// that the upload is ordered on the caller's stream like the kernel behind it; the next call waits for the previous upload only.
+namespace {
+struct ResizeStage {
+  int* host = nullptr;
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool pending = false;
+};
+thread_local ResizeStage g_resize_stage;
+}  // namespace
+
+extern "C" int64_t mn_op_resize_work_bytes(int src_h, int src_w, int H, int W) {
+  if (src_h < 1 || src_w < 1 || H < 1 || W < 1) {
+    fail("mn_op_resize_work_bytes: source and output sizes must be positive");
+    return -1;
+  }
+  return resize_table_bytes(src_h, src_w, H, W);
+}
+
+extern "C" int mn_op_resize_tile(int src_h, int src_w, int H, int W, int* tile_h, int* tile_w) {
+  if (!tile_h || !tile_w) return fail("mn_op_resize_tile: tile_h and tile_w are required");
+  const ResizePlan rp = resize_plan(1, src_h, src_w, H, W, nullptr);
+  if (!rp.error.empty()) return fail("mn_op_resize_tile: " + rp.error);
+  *tile_h = rp.g.th;
+  *tile_w = rp.g.tw;
+  return 0;
+}
+
+extern "C" int mn_op_resize_u8(const unsigned char* in, unsigned char* out, void* work, int B, int src_h, int src_w, int H, int W,
+                               void* stream) {
+  begin_op();
+  if (!in || !out || !work) return fail("mn_op_resize_u8: in, out and work are required");
+  if (((uintptr_t)work & 3) != 0) return fail("mn_op_resize_u8: work must be 4-byte aligned");
+  const ResizePlan rp = resize_plan(B, src_h, src_w, H, W, (int*)work);
+  if (!rp.error.empty()) return fail("mn_op_resize_u8: " + rp.error);
+  ResizeStage& st = g_resize_stage;
+  const size_t bytes = rp.tables.size() * sizeof(int);
+  if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) return check_launch("resize_u8 (event)");
+  if (st.pending) {
+    (void)hipEventSynchronize(st.ev);
+    st.pending = false;
+  }
+  if (st.cap < bytes) {
+    if (st.host) (void)hipHostFree(st.host);
+    st.host = nullptr;
+    st.cap = 0;
+    if (hipHostMalloc((void**)&st.host, bytes, 0) != hipSuccess) return check_launch("resize_u8 (pinned tables)");
+    st.cap = bytes;
+  }
+  memcpy(st.host, rp.tables.data(), bytes);
+  hipMemcpyAsync(work, st.host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
+  hipEventRecord(st.ev, (hipStream_t)stream);
+  st.pending = true;
+  launch_resize_u8(in, out, rp.g, (hipStream_t)stream);
+  return check_launch("resize_u8");
 }
 
 extern "C" int mn_op_stem_dgrad(int dtype, const void* gy, const void* w, float* gx, int B, int H, int W, float alpha, void* stream) {

@@ -13,6 +13,22 @@ import torch
 from .evaluate import qexp
 
 
+def resize_dims(h, w, size):
+    """(H, W) that torchvision's `transforms.Resize(size)` gives an h x w frame (the first entry of the reference's image transform,
+    scripts/train.py:120-128): an int makes the smaller edge `size` and the other int(size * long / short) -- (480, 640, 256) ->
+    (256, 341), (640, 480, 256) -> (341, 256); a pair (H, W) is taken as given."""
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError("resize_dims: size must be an int or a pair (H, W)")
+        return int(size[0]), int(size[1])
+    h, w, size = int(h), int(w), int(size)
+    if h < 1 or w < 1 or size < 1:
+        raise ValueError("resize_dims: sizes must be positive")
+    if w <= h:
+        return int(size * h / w), size
+    return size, int(size * w / h)
+
+
 def qlog(q):
     """logarithm map (4,) -> (3,)   (pose_utils.py:306-317)"""
     q = np.asarray(q)

@@ -109,6 +109,8 @@ class Engine:
         # all 0: off.  jitter_calls: jittered forward passes of this model so far, whichever plan ran them (the Philox counter)
         self.color_jitter = (0.0, 0.0, 0.0, 0.0, 0)
         self.jitter_calls = 0
+        # the `size` of the device Resize on uint8 input (mn_set_input_resize; data.resize_dims): an int, a pair (H, W), None = off
+        self.input_resize = None
 
     # -- arenas ---------------------------------------------------------------------------------
     @property
@@ -178,11 +180,12 @@ class Engine:
         return self.params[self.n_model:]
 
     # -- plans ------------------------------------------------------------------------------------
-    def plan(self, mode, windows, T, H, W):
+    def plan(self, mode, windows, T, H, W, src=None):
+        """src: (h, w) of the source frames when the device Resize is on (source_dims), else None"""
         self._check_device()
         dtype = self.dtype or _default_dtype
         scale = self.loss_scale if self.loss_scale is not None else (_default_loss_scale if dtype in SCALED_DTYPES else 1.0)
-        key = (mode, windows, T, H, W, dtype, scale, self.eps_mode)
+        key = (mode, windows, T, H, W, dtype, scale, self.eps_mode) + (() if src is None else (tuple(src),))
         p = self.plans.get(key)
         if p is None:
             self.ensure_opt_state()
@@ -200,6 +203,18 @@ class Engine:
             frames = 1 if mode == MODE_POSENET else (T if mode == MODE_MAPNET else 2 * T)
             p = {"handle": C.c_void_p(h), "work": work, "version": self.version, "cfg": cfg, "images": windows * frames,
                  "loss": torch.zeros(1, dtype=torch.float32, device=self.device), "dtype": dtype}
+            if src is not None:  # the resized frames and the coefficient tables: per plan, like the work arena
+                nres = int(self.lib.input_resize_bytes(C.byref(cfg), int(src[0]), int(src[1])))
+                if nres < 0:
+                    self.lib.destroy(p["handle"])
+                    raise MapNetHipError(self.lib.last_error().decode())
+                p["resize_work"] = torch.empty(nres, dtype=torch.uint8, device=self.device)
+                rc = self.lib.set_input_resize(p["handle"], int(src[0]), int(src[1]), ptr(p["resize_work"]), nres)
+                if rc != 0:
+                    msg = self.lib.last_error().decode()
+                    self.lib.destroy(p["handle"])
+                    raise MapNetHipError(msg)
+                p["src"] = tuple(src)
             self.plans[key] = p
         if p["version"] != self.version:
             self.lib.check(self.lib.params_changed(p["handle"]))
@@ -342,11 +357,42 @@ class Engine:
         """images become uint8 [.., H, W, 3]; (x/255 - mean)/std runs on the device.  mean=None: back to fp32 NCHW."""
         self.input_u8 = None if mean is None else (tuple(float(v) for v in mean), tuple(float(v) for v in std))
 
+    def set_input_resize(self, size):
+        """torchvision's Resize(size) -- PIL's bilinear resample, bit for bit -- on the device, ahead of everything else the input
+        path does (include/mapnet_hip.h mn_set_input_resize).  size: an int (smaller edge), a pair (H, W), or None = off.  Needs
+        set_input_u8: the frames arrive as uint8 [.., h, w, 3] of any size; each source size gets a plan of its own."""
+        if size is None:
+            self.input_resize = None
+            return
+        if self.input_u8 is None:
+            raise MapNetHipError("set_input_resize needs uint8 input (call set_input_u8 first): Resize comes before Normalize, and "
+                                 "fp32 frames arrive normalised")
+        size = tuple(int(v) for v in size) if isinstance(size, (tuple, list)) else int(size)
+        if (len(size) != 2 or min(size) < 1) if isinstance(size, tuple) else size < 1:
+            raise MapNetHipError("set_input_resize: size must be a positive int or a pair (H, W) of them")
+        self.input_resize = size
+
+    def source_dims(self, images):
+        """-> (h, w) of the frames as they arrive when the device Resize is on, else None: the `src` of plan()"""
+        if self.input_resize is None or self.input_u8 is None:
+            return None
+        return int(images.shape[-3]), int(images.shape[-2])
+
+    def resized_frames(self, plan):
+        """uint8 [images, H, W, 3]: the frames the last pass of `plan` resampled (a copy; scripts/plot_activations.py, tests)"""
+        cfg = plan["cfg"]
+        n = plan["images"] * cfg.H * cfg.W * 3
+        return plan["resize_work"][:n].view(plan["images"], cfg.H, cfg.W, 3).clone()
+
     def image_dims(self, images):
-        """-> (H, W) of one frame, for either input format; validates the dtype against the configured format"""
+        """-> (H, W) of one frame as the network sees it, for either input format (with the device Resize on: the plan's dims, from
+        the frames' own); validates the dtype against the configured format"""
         if self.input_u8 is not None:
             if images.dtype != torch.uint8 or images.shape[-1] != 3:
                 raise MapNetHipError("uint8 input mode expects uint8 images [..., H, W, 3]")
+            if self.input_resize is not None:
+                from .data import resize_dims
+                return resize_dims(int(images.shape[-3]), int(images.shape[-2]), self.input_resize)
             return int(images.shape[-3]), int(images.shape[-2])
         if images.dtype != torch.float32:
             raise MapNetHipError("expected fp32 images [..., 3, H, W] (or call set_input_u8 for uint8 NHWC input)")
@@ -356,7 +402,7 @@ class Engine:
         """images: fp32 [B,3,H,W] (or uint8 [B,H,W,3]) contiguous on the engine's device -> poses [B,6]."""
         B = images.shape[0]
         H, W = self.image_dims(images)
-        p = self.plan(MODE_POSENET, B, 1, H, W)
+        p = self.plan(MODE_POSENET, B, 1, H, W, self.source_dims(images))
         out = torch.empty(B, 6, dtype=torch.float32, device=self.device)
         self._jitter_pass(p)
         self.lib.check(self.lib.forward(p["handle"], ptr(images), ptr(out), int(bool(training)), _stream(images)))
@@ -383,7 +429,7 @@ class Engine:
             if tuple(cotangent.shape) != (B, 6):
                 raise ValueError("input_grad: cotangent must have shape [%d, 6], got %s" % (B, list(cotangent.shape)))
             cot = cotangent.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        p = self.plan(MODE_POSENET, B, 1, H, W)
+        p = self.plan(MODE_POSENET, B, 1, H, W, self.source_dims(x))
         gx = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
         poses = torch.empty(B, 6, dtype=torch.float32, device=self.device)
         maps = torch.empty(B, H, W, dtype=torch.float32, device=self.device) if saliency else None

@@ -222,6 +222,12 @@ class PoseNet(_ArenaModule):
         it off.  Draws are keyed by `seed` and the model's count of jittered passes (include/mapnet_hip.h mn_set_color_jitter)."""
         self._engine.set_color_jitter(brightness, contrast, saturation, hue, seed)
 
+    def set_input_resize(self, size=256):
+        """torchvision's `transforms.Resize(size)` on the device, for uint8 input (set_input_u8): frames arrive at the size the dataset
+        decodes them to and are resampled exactly as PIL resamples them (bilinear, 8-bit fixed point) before ColorJitter, ToTensor and
+        Normalize.  size: int (smaller edge -> size, data.resize_dims) or (H, W); None turns it off."""
+        self._engine.set_input_resize(size)
+
     def forward(self, x):
         u8 = self._engine.input_u8 is not None
         if x.dim() != 4 or (x.shape[-1] if u8 else x.shape[1]) != 3:
@@ -289,6 +295,9 @@ class MapNet(nn.Module):
 
     def set_color_jitter(self, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, seed=0):
         self.mapnet.set_color_jitter(brightness, contrast, saturation, hue, seed)
+
+    def set_input_resize(self, size=256):
+        self.mapnet.set_input_resize(size)
 
     def load_state_dict(self, state_dict, strict=True):
         r = super().load_state_dict(state_dict, strict)

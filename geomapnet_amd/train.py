@@ -61,7 +61,7 @@ def step_feedfwd(data, model, cuda, target=None, criterion=None, optim=None, tra
     # the fused kernel indexes the target as [n][rows of this criterion][6]: a wrong layout must not reach the device
     criterion.check_batch(n, data.shape[1] if mode != MODE_POSENET else 1, target)
     _bind(engine, criterion, optim)
-    plan = engine.plan(mode, n, t, H, W)
+    plan = engine.plan(mode, n, t, H, W, engine.source_dims(data))
     lr, wd, betas, eps = optim.learner.hyper()
     engine.configure_step(plan, lr, wd, betas, eps, float(max_grad_norm), criterion.learn_beta, criterion.learn_gamma,
                           method=optim.learner.method())

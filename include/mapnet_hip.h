@@ -201,6 +201,24 @@ int mn_set_color_jitter(mn_handle* h, float brightness, float contrast, float sa
  * replays the draws from 0; data-parallel ranks pass different seeds (scripts/train.py: seed ^ rank << 32). */
 int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls);
 
+/* Resize on the device for uint8 input: replaces `transforms.Resize(256)`, the first entry of the reference's image transform
+ * (scripts/train.py:120-128, scripts/eval.py:99, scripts/plot_activations.py:68).  Semantics: PIL's
+ * Image.fromarray(frame).resize((W, H), Image.BILINEAR) per frame, bit for bit -- Pillow's two-pass resample in 8-bit fixed point
+ * (22 fractional bits; horizontal pass first and rounded to uint8, then the vertical pass; an axis whose size does not change has no
+ * pass), with the coefficient tables computed in double on the host as Pillow computes them.  H x W are the plan's (mn_config).
+ * mn_input_resize_bytes: bytes of the caller-owned device buffer `work` for source frames of src_h x src_w: the resized frames
+ * [images][H][W][3] at offset 0, then the tables; -1 on bad sizes.  mn_set_input_resize: src_h = src_w = 0 turns the resize off
+ * (work is ignored); otherwise the `images` argument of mn_forward / mn_train_step / mn_train_forward_loss / mn_input_grad is uint8
+ * NHWC [images][src_h][src_w][3], resampled into `work` by one kernel at the head of the pass, and everything downstream -- the
+ * uint8 conversion of mn_set_input_u8, the ColorJitter chain with its contrast mean, the x of mn_input_grad's saliency map -- reads
+ * the resized frames where it read `images`.  gx_out / saliency_out of mn_input_grad stay H x W.  The call waits for the device and
+ * writes the tables into `work`; `work` must stay valid until the resize is turned off or the plan destroyed.  mn_plan_bytes and
+ * the work arena are unchanged; a plan with the resize off launches exactly what it launched before.  Fails on non-positive sizes,
+ * a NULL or too small `work`, a shrink whose single-pixel source band exceeds LDS (beyond ~60x); a forward pass with the resize on and
+ * fp32 input fails: Resize comes before Normalize, and fp32 frames arrive normalised. */
+int64_t mn_input_resize_bytes(const mn_config* cfg, int src_h, int src_w);
+int mn_set_input_resize(mn_handle* h, int src_h, int src_w, void* work, int64_t work_bytes);
+
 /* Attention maps: replaces `data_var = Variable(data, requires_grad=True); pose = model(data_var); pose.mean().backward();
  * data_var.grad` of scripts/plot_activations.py:117-123, with model.eval() (plot_activations.py:50).  Runs the eval forward pass
  * and the data-gradient chain alone: BatchNorm on running statistics (a per-channel scale), no weight gradients, no optimiser.
@@ -453,6 +471,14 @@ int mn_op_maxpool_bwd(int dtype, const unsigned char* idx, const void* gout, voi
  * hue; mean / std: 3 floats each in host memory; work: B * 9 floats of device memory (gray partials and means). */
 int mn_op_color_jitter(const unsigned char* in, float* out, float* draws, float* work, int B, int H, int W, const float* ranges,
                        uint64_t seed, uint32_t call, const float* mean, const float* std, void* stream);
+
+/* the resample of mn_set_input_resize on its own (transforms.Resize of scripts/train.py:120-128 = PIL Image.resize, BILINEAR):
+ * in uint8 NHWC [B][src_h][src_w][3] -> out uint8 NHWC [B][H][W][3], B <= 65535.  work: mn_op_resize_work_bytes() bytes of device
+ * memory (4-byte aligned) for the coefficient tables, which every call computes on the host and uploads on `stream` ahead of its
+ * kernel.  mn_op_resize_tile: the output rows x columns a workgroup owns at these sizes (tests, tools). */
+int mn_op_resize_u8(const unsigned char* in, unsigned char* out, void* work, int B, int src_h, int src_w, int H, int W, void* stream);
+int64_t mn_op_resize_work_bytes(int src_h, int src_w, int H, int W);
+int mn_op_resize_tile(int src_h, int src_w, int H, int W, int* tile_h, int* tile_w);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (no counterpart in the reference, which is single-device: common/train.py:91-92).

@@ -44,6 +44,10 @@ def build_parser():
     parser.add_argument("--synthetic_length", type=int, default=256)
     parser.add_argument("--u8_input", action="store_true", help="frames as uint8 [H,W,3]; ToTensor + Normalize run on the "
                         "device (model.set_input_u8)")
+    parser.add_argument("--device_resize", type=int, default=None, metavar="SIZE",
+                        help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
+                             "transform): the dataset yields frames of --height x --width and the network runs at the resized "
+                             "size; needs --u8_input")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     return parser
@@ -58,6 +62,9 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
     from geomapnet_amd import evaluate as E
     from geomapnet_amd.data import MF, SyntheticFrames, calc_vos_safe, calc_vos_safe_fc
 
+    if args.device_resize is not None and not args.u8_input:
+        raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 frames "
+                         "arrive normalised)")
     if "CUDA_VISIBLE_DEVICES" not in os.environ:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.device
     G.set_compute_dtype(args.dtype)
@@ -91,6 +98,8 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
     model.eval()
     if args.u8_input:
         model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
+    if args.device_resize is not None:
+        model.set_input_resize(args.device_resize)
 
     # load weights
     weights_filename = osp.expanduser(args.weights)

@@ -70,6 +70,10 @@ def build_parser():
                         help="apply the config's color_jitter as torchvision's ColorJitter(cj, cj, cj, hue=0.5) on the device, "
                              "to training and validation frames (the reference's transform, scripts/train.py:121-125); needs "
                              "--u8_input.  Without this flag color_jitter is read and not applied")
+    parser.add_argument("--device_resize", type=int, default=None, metavar="SIZE",
+                        help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
+                             "transform, scripts/train.py:120): the dataset yields frames of --height x --width and the network runs "
+                             "at the resized size; needs --u8_input")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     parser.add_argument("--epochs", type=int, default=None, help="override [training] n_epochs")
@@ -157,6 +161,11 @@ def run(args, datasets=None, _binding=None, log=print):
 
     if args.u8_input:  # the DataLoader ships decoded frames; normalisation happens in the input-conversion kernel
         model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
+    if args.device_resize is not None:
+        if not args.u8_input:
+            raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 "
+                             "frames arrive normalised)")
+        model.set_input_resize(args.device_resize)
     if args.device_color_jitter and color_jitter > 0:
         assert color_jitter <= 1.0
         if not args.u8_input:
