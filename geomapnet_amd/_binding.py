@@ -45,6 +45,7 @@ _PROTOS = {
     "mn_create": (c_void, [C.POINTER(Config), c_void, c_void, c_void, c_void, c_void]),
     "mn_destroy": (None, [c_void]),
     "mn_set_learn_flags": (c_i, [c_void, c_i, c_i]),
+    "mn_set_loss_fn": (c_i, [c_void, c_i, c_f, c_i, c_f]),
     "mn_set_optim": (c_i, [c_void, c_f, c_f, c_f, c_f, c_f, c_f]),
     "mn_set_optim_method": (c_i, [c_void, c_i, c_i]),
     "mn_set_step_count": (c_i, [c_void, c_i64]),
@@ -99,6 +100,8 @@ _PROTOS = {
                                       c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_f, c_void]),
     "mn_op_oihw_to_ohwi": (c_i, [c_void, c_void, c_i, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_criterion": (c_i, [c_i, c_i, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_f, c_void]),
+    "mn_op_criterion_fn": (c_i, [c_i, c_i, c_i, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_f, c_i, c_f, c_i, c_f,
+                                 c_void]),
     "mn_op_calc_vos": (c_i, [c_void, c_i, c_i, c_void, c_void, c_void, c_void]),
     "mn_pgo_optimize": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
                               C.c_double, c_i, c_void]),

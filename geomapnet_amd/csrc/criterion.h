@@ -13,8 +13,11 @@
 // norm has zero gradient at 0, acos' -1/sqrt(1-x^2) is allowed to produce inf/NaN), so the
 // NaN hazard of coincident rotations is reproduced, not hidden.
 //
+// t_loss_fn / q_loss_fn (:34,55,112) are nn.L1Loss by default; criterion_kernel<true> takes nn.MSELoss, nn.SmoothL1Loss,
+// nn.HuberLoss for either and QuaternionLoss (:15-31) for the rotation (enum mn_loss_kind, LossFns below).
+//
 // One workgroup of 256 threads; thread n-strides over windows; block reduction of the four
-// L1 sums in fp64.  d(pred) is written multiplied by `grad_scale` (the fp16 loss scale).
+// loss sums in fp64.  d(pred) is written multiplied by `grad_scale` (the fp16 loss scale).
 #pragma once
 #include "common.h"
 
@@ -172,6 +175,44 @@ __device__ __forceinline__ void vo_logq(const float* p0, const float* p1, float*
 
 __device__ __forceinline__ float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
+// Per-element loss functions (t_loss_fn / q_loss_fn of common/criterion.py:34,55,112), torch's formulas with mean reduction;
+// the numbers are enum mn_loss_kind of include/mapnet_hip.h.  kLossQuaternion (QuaternionLoss, common/criterion.py:15-31) is a
+// rotation kind only and works on a row of three components at a time.
+enum { kLossL1 = 0, kLossMSE = 1, kLossSmoothL1 = 2, kLossHuber = 3, kLossQuaternion = 4 };
+
+// nullptr, or why (t_kind, t_param, q_kind, q_param) is refused (shared by mn_op_criterion_fn and mn_set_loss_fn)
+inline const char* loss_fn_error(int t_kind, float t_param, int q_kind, float q_param) {
+  if (t_kind == kLossQuaternion) return "the quaternion loss is a rotation loss (q_kind) only";
+  if (t_kind < kLossL1 || t_kind > kLossHuber) return "unknown t_kind (enum mn_loss_kind)";
+  if (q_kind < kLossL1 || q_kind > kLossQuaternion) return "unknown q_kind (enum mn_loss_kind)";
+  if (!(t_param >= 0.f) || !(q_param >= 0.f)) return "a loss parameter (beta / delta) must be >= 0";
+  return nullptr;
+}
+
+// value of one element's loss at d = pred - targ; dv = its derivative with respect to d (torch's backward formulas: the
+// quadratic piece of SmoothL1 / Huber owns |d| == param, sgn(0) = 0; SmoothL1 with beta == 0 is L1)
+__device__ __forceinline__ float loss_elem(int kind, float prm, float d, float& dv) {
+  const float ad = fabsf(d);
+  if (kind == kLossMSE) {
+    dv = 2.f * d;
+    return d * d;
+  }
+  if (kind == kLossSmoothL1 && ad < prm) {
+    dv = d / prm;
+    return 0.5f * d * d / prm;
+  }
+  if (kind == kLossHuber) {
+    if (ad <= prm) {
+      dv = d;
+      return 0.5f * d * d;
+    }
+    dv = prm * sgn(d);
+    return prm * (ad - 0.5f * prm);
+  }
+  dv = sgn(d);
+  return (kind == kLossSmoothL1) ? ad - 0.5f * prm : ad;
+}
+
 struct CriterionArgs {
   int mode;            // 0 posenet, 1 mapnet, 2 online, 3 online-gps
   int N, T;            // windows, frames per (absolute) window
@@ -183,12 +224,41 @@ struct CriterionArgs {
   float* ds;           // [4] accumulated (+=) d loss / d s, or null
   float* vos_out;      // optional: predicted relative poses [N][T-1][6] (modes 1,2), for tests
   float grad_scale;
+  // read by criterion_kernel<true> only: loss kind and parameter (SmoothL1's beta, Huber's delta) of the translation and of the
+  // rotation components
+  int t_kind = kLossL1, q_kind = kLossL1;
+  float t_param = 0.f, q_param = 0.f;
+};
+
+// the loss functions of one launch; kFn == false is L1 / L1 with the kinds folded at compile time (the launch every caller
+// that never chose a loss function gets)
+template <bool kFn>
+struct LossFns {
+  int tk, qk;
+  float tp, qp;
+  __device__ __forceinline__ explicit LossFns(const CriterionArgs& a)
+      : tk(kFn ? a.t_kind : (int)kLossL1), qk(kFn ? a.q_kind : (int)kLossL1), tp(kFn ? a.t_param : 0.f), qp(kFn ? a.q_param : 0.f) {}
+  __device__ __forceinline__ bool quaternion() const { return kFn && qk == kLossQuaternion; }
+  // one row of six components p against g: translation values into st, rotation values into sq, derivatives with respect to p
+  // into dv.  The quaternion kind is 1 - (p.g)^2 per row with gradient -2 (p.g) g.
+  __device__ __forceinline__ void row(const float* p, const float* g, double& st, double& sq, float* dv) const {
+    for (int c = 0; c < 3; ++c) st += loss_elem(tk, tp, p[c] - g[c], dv[c]);
+    if (quaternion()) {
+      const float pg = (p[3] * g[3] + p[4] * g[4]) + p[5] * g[5];
+      sq += 1.0 - (double)pg * (double)pg;
+      for (int c = 3; c < 6; ++c) dv[c] = -2.f * pg * g[c];
+    } else {
+      for (int c = 3; c < 6; ++c) sq += loss_elem(qk, qp, p[c] - g[c], dv[c]);
+    }
+  }
 };
 
 constexpr int kMaxT = 8;
 
+template <bool kFn>
 static __global__ void __launch_bounds__(256) criterion_kernel(CriterionArgs a) {
   __shared__ double red[4][4];
+  const LossFns<kFn> fn(a);
   const int T = a.T, N = a.N;
   const int Tp = (a.mode >= 2) ? 2 * T : (a.mode == 0 ? 1 : T);       // pred rows per window
   const int Tg = (a.mode == 2) ? 2 * T - 1 : Tp;                      // targ rows per window
@@ -202,7 +272,10 @@ static __global__ void __launch_bounds__(256) criterion_kernel(CriterionArgs a) 
   } else {
     n_vo_t = n_vo_q = 3.f * (float)N * (float)(T - 1);
   }
-  const float w_at = expf(-sax) / n_abs, w_aq = expf(-saq) / n_abs;
+  // the rotation means: over elements, or over rows of three (the quaternion kind)
+  const float n_abs_q = fn.quaternion() ? (float)N * (float)((a.mode == 0) ? 1 : T) : n_abs;
+  if (fn.quaternion() && a.mode != 3) n_vo_q = (float)N * (float)(T - 1);
+  const float w_at = expf(-sax) / n_abs, w_aq = expf(-saq) / n_abs_q;
   const float w_vt = expf(-srx) / n_vo_t, w_vq = expf(-srq) / n_vo_q;
   double sum[4] = {0, 0, 0, 0};  // At, Aq, Vt, Vq
 
@@ -213,42 +286,42 @@ static __global__ void __launch_bounds__(256) criterion_kernel(CriterionArgs a) 
     for (int i = 0; i < Tp; ++i)
       for (int c = 0; c < 6; ++c) grad[i][c] = 0.f;
     const int Tabs = (a.mode == 0) ? 1 : T;
-    for (int i = 0; i < Tabs; ++i)
-      for (int c = 0; c < 6; ++c) {
-        float d = p[i * 6 + c] - g[i * 6 + c];
-        sum[c < 3 ? 0 : 1] += fabsf(d);
-        grad[i][c] += (c < 3 ? w_at : w_aq) * sgn(d);
-      }
+    for (int i = 0; i < Tabs; ++i) {
+      float dv[6];
+      fn.row(p + i * 6, g + i * 6, sum[0], sum[1], dv);
+      for (int c = 0; c < 6; ++c) grad[i][c] += (c < 3 ? w_at : w_aq) * dv[c];
+    }
     if (a.mode == 1) {
-      for (int i = 0; i + 1 < T; ++i)
+      for (int i = 0; i + 1 < T; ++i) {
+        float pv[6], gv[6], dv[6];
         for (int c = 0; c < 6; ++c) {
-          float pv = p[(i + 1) * 6 + c] - p[i * 6 + c];
-          float gv = g[(i + 1) * 6 + c] - g[i * 6 + c];
-          float d = pv - gv;
-          if (a.vos_out) a.vos_out[((long)n * (T - 1) + i) * 6 + c] = pv;
-          sum[c < 3 ? 2 : 3] += fabsf(d);
-          float w = (c < 3 ? w_vt : w_vq) * sgn(d);
+          pv[c] = p[(i + 1) * 6 + c] - p[i * 6 + c];
+          gv[c] = g[(i + 1) * 6 + c] - g[i * 6 + c];
+          if (a.vos_out) a.vos_out[((long)n * (T - 1) + i) * 6 + c] = pv[c];
+        }
+        fn.row(pv, gv, sum[2], sum[3], dv);
+        for (int c = 0; c < 6; ++c) {
+          float w = (c < 3 ? w_vt : w_vq) * dv[c];
           grad[i + 1][c] += w;
           grad[i][c] -= w;
         }
+      }
     } else if (a.mode == 2) {
       for (int i = 0; i + 1 < T; ++i) {
-        float u[6], ub[6];
+        float u[6], ub[6], dv[6];
         vo_logq(p + (T + i) * 6, p + (T + i + 1) * 6, u, nullptr, nullptr, nullptr, false);
-        for (int c = 0; c < 6; ++c) {
-          float d = u[c] - g[(T + i) * 6 + c];
-          if (a.vos_out) a.vos_out[((long)n * (T - 1) + i) * 6 + c] = u[c];
-          sum[c < 3 ? 2 : 3] += fabsf(d);
-          ub[c] = (c < 3 ? w_vt : w_vq) * sgn(d);
-        }
+        if (a.vos_out)
+          for (int c = 0; c < 6; ++c) a.vos_out[((long)n * (T - 1) + i) * 6 + c] = u[c];
+        fn.row(u, g + (T + i) * 6, sum[2], sum[3], dv);
+        for (int c = 0; c < 6; ++c) ub[c] = (c < 3 ? w_vt : w_vq) * dv[c];
         if (want_grad) vo_logq(p + (T + i) * 6, p + (T + i + 1) * 6, u, ub, grad[T + i], grad[T + i + 1], true);
       }
     } else if (a.mode == 3) {
       for (int i = 0; i < T; ++i)
         for (int c = 0; c < 2; ++c) {
-          float d = p[(T + i) * 6 + c] - g[(T + i) * 6 + c];
-          sum[2] += fabsf(d);
-          grad[T + i][c] += w_vt * sgn(d);
+          float dv;
+          sum[2] += loss_elem(fn.tk, fn.tp, p[(T + i) * 6 + c] - g[(T + i) * 6 + c], dv);
+          grad[T + i][c] += w_vt * dv;
         }
     }
     if (want_grad)
@@ -267,7 +340,7 @@ static __global__ void __launch_bounds__(256) criterion_kernel(CriterionArgs a) 
       tot[k] = 0;
       for (int w = 0; w < nw; ++w) tot[k] += red[w][k];
     }
-    float At = (float)(tot[0] / n_abs), Aq = (float)(tot[1] / n_abs);
+    float At = (float)(tot[0] / n_abs), Aq = (float)(tot[1] / n_abs_q);
     float Vt = (float)(tot[2] / n_vo_t), Vq = (float)(tot[3] / n_vo_q);
     float ea = expf(-sax), eq = expf(-saq), ex = expf(-srx), er = expf(-srq);
     float loss = (ea * At + sax) + (eq * Aq + saq);

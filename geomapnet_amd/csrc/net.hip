@@ -288,6 +288,9 @@ struct PlanBase {
   int64_t step = 0;
   bool weights_dirty = true;
   int learn_beta = 0, learn_gamma = 0;
+  // t_loss_fn / q_loss_fn of the criterion (mn_set_loss_fn; enum mn_loss_kind) and SmoothL1's beta / Huber's delta
+  int t_kind = MN_LOSS_L1, q_kind = MN_LOSS_L1;
+  float t_param = 0.f, q_param = 0.f;
   KernelTimer timer;
 };
 
@@ -917,7 +920,11 @@ struct Plan : PlanBase {
     CriterionArgs a;
     a.mode = cfg.mode; a.N = cfg.windows; a.T = cfg.T; a.pred = pred; a.targ = targ; a.s = params + L.crit; a.loss = loss;
     a.dpred = dpred; a.ds = ds; a.vos_out = nullptr; a.grad_scale = cur_scale;
-    hipLaunchKernelGGL(criterion_kernel, dim3(1), dim3(256), 0, s, a);
+    a.t_kind = t_kind; a.t_param = t_param; a.q_kind = q_kind; a.q_param = q_param;
+    if (t_kind == kLossL1 && q_kind == kLossL1)  // (the default: the kinds folded at compile time)
+      hipLaunchKernelGGL(criterion_kernel<false>, dim3(1), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(criterion_kernel<true>, dim3(1), dim3(256), 0, s, a);
   }
   int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) override {
     run_criterion(pred, targ, loss_out, nullptr, nullptr, s);
@@ -1470,6 +1477,15 @@ extern "C" int mn_set_learn_flags(mn_handle* h, int learn_beta, int learn_gamma)
     static_cast<Plan<half>&>(P).update_frozen(nullptr);
   else
     static_cast<Plan<float>&>(P).update_frozen(nullptr);
+  return 0;
+}
+extern "C" int mn_set_loss_fn(mn_handle* h, int t_kind, float t_param, int q_kind, float q_param) {
+  MN_H(h);
+  if (const char* why = loss_fn_error(t_kind, t_param, q_kind, q_param)) return fail(std::string("mn_set_loss_fn: ") + why);
+  P.t_kind = t_kind;
+  P.t_param = t_param;
+  P.q_kind = q_kind;
+  P.q_param = q_param;
   return 0;
 }
 extern "C" int mn_set_optim(mn_handle* h, float lr, float weight_decay, float beta1, float beta2, float eps,

@@ -263,16 +263,39 @@ extern "C" int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, in
   return check_launch("oihw_ohwi");
 }
 
-extern "C" int mn_op_criterion(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss,
-                               float* dpred, float* ds, float* vos_out, float grad_scale, void* stream) {
-  begin_op();
+static_assert(kLossL1 == MN_LOSS_L1 && kLossMSE == MN_LOSS_MSE && kLossSmoothL1 == MN_LOSS_SMOOTH_L1 && kLossHuber == MN_LOSS_HUBER &&
+                  kLossQuaternion == MN_LOSS_QUATERNION,
+              "criterion.h's kinds are enum mn_loss_kind");
+
+static int op_criterion(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss, float* dpred,
+                        float* ds, float* vos_out, float grad_scale, int t_kind, float t_param, int q_kind, float q_param,
+                        void* stream) {
   if (T < 1 || T > kMaxT) return fail("criterion: T out of range");
   if (mode < 0 || mode > 3) return fail("criterion: bad mode");
+  if (const char* why = loss_fn_error(t_kind, t_param, q_kind, q_param)) return fail(std::string("criterion: ") + why);
   CriterionArgs a;
   a.mode = mode; a.N = N; a.T = T; a.pred = pred; a.targ = targ; a.s = s; a.loss = loss; a.dpred = dpred; a.ds = ds;
   a.vos_out = vos_out; a.grad_scale = grad_scale;
-  hipLaunchKernelGGL(criterion_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  a.t_kind = t_kind; a.t_param = t_param; a.q_kind = q_kind; a.q_param = q_param;
+  if (t_kind == kLossL1 && q_kind == kLossL1)
+    hipLaunchKernelGGL(criterion_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(criterion_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("criterion");
+}
+
+extern "C" int mn_op_criterion(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss,
+                               float* dpred, float* ds, float* vos_out, float grad_scale, void* stream) {
+  begin_op();
+  return op_criterion(mode, N, T, pred, targ, s, loss, dpred, ds, vos_out, grad_scale, kLossL1, 0.f, kLossL1, 0.f, stream);
+}
+
+extern "C" int mn_op_criterion_fn(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss,
+                                  float* dpred, float* ds, float* vos_out, float grad_scale, int t_kind, float t_param,
+                                  int q_kind, float q_param, void* stream) {
+  begin_op();
+  return op_criterion(mode, N, T, pred, targ, s, loss, dpred, ds, vos_out, grad_scale, t_kind, t_param, q_kind, q_param,
+                      stream);
 }
 
 extern "C" int mn_op_calc_vos(const float* poses, int N, int T, float* vos, const float* cot, float* dposes,

@@ -440,8 +440,21 @@ class Engine:
                                  % (p["dtype"], p["cfg"].loss_scale))
         return gx, poses, maps
 
-    def configure_step(self, p, lr, weight_decay, betas, eps, max_grad_norm, learn_beta, learn_gamma, method=(0, 0)):
+    L1_L1 = (0, 0.0, 0, 0.0)  # a new plan's loss functions (mn_set_loss_fn)
+
+    def set_loss_fn(self, p, loss_fn):
+        """loss_fn = (t_kind, t_param, q_kind, q_param), a criterion's `.loss_fn`: what the criterion of plan `p` evaluates from the
+        next call on (mn_train_step, mn_train_forward_loss, mn_loss); the library is told only when it differs from the plan's
+        current setting, so a train and a validation criterion with different losses can alternate on one model"""
+        loss_fn = (int(loss_fn[0]), float(loss_fn[1]), int(loss_fn[2]), float(loss_fn[3]))
+        if p.get("loss_fn", self.L1_L1) != loss_fn:
+            self.lib.check(self.lib.set_loss_fn(p["handle"], loss_fn[0], C.c_float(loss_fn[1]), loss_fn[2], C.c_float(loss_fn[3])))
+            p["loss_fn"] = loss_fn
+
+    def configure_step(self, p, lr, weight_decay, betas, eps, max_grad_norm, learn_beta, learn_gamma, method=(0, 0),
+                       loss_fn=L1_L1):
         h = p["handle"]
+        self.set_loss_fn(p, loss_fn)
         self.lib.check(self.lib.set_optim(h, lr, weight_decay, betas[0], betas[1], eps, max_grad_norm))
         if p.get("method", (0, 0)) != tuple(method):
             self.lib.check(self.lib.set_optim_method(h, int(method[0]), int(method[1])))

@@ -64,7 +64,7 @@ def step_feedfwd(data, model, cuda, target=None, criterion=None, optim=None, tra
     plan = engine.plan(mode, n, t, H, W, engine.source_dims(data))
     lr, wd, betas, eps = optim.learner.hyper()
     engine.configure_step(plan, lr, wd, betas, eps, float(max_grad_norm), criterion.learn_beta, criterion.learn_gamma,
-                          method=optim.learner.method())
+                          method=optim.learner.method(), loss_fn=criterion.loss_fn)
     if dp.world_size() > 1 or _FORCE_STAGED:
         loss, poses = dp.train_step(engine, plan, data, target)
     else:

@@ -75,6 +75,17 @@ enum {
   MN_MODE_MAPNET_ONLINE = 2,/* MapNetOnlineCriterion,   common/criterion.py:111-184 */
   MN_MODE_MAPNET_GPS = 3    /* ... with gps_mode=True,  common/criterion.py:166,173-180 */
 };
+/* t_loss_fn / q_loss_fn of the three criteria (common/criterion.py:34,55,112: any callable, nn.L1Loss() by default).  The
+ * kinds below are evaluated on the device, each with torch's formula and mean reduction; `param` is SmoothL1Loss.beta or
+ * HuberLoss.delta and is ignored by the other kinds. */
+enum mn_loss_kind {
+  MN_LOSS_L1 = 0,        /* nn.L1Loss:        |d|                                                     */
+  MN_LOSS_MSE = 1,       /* nn.MSELoss:       d^2                                                     */
+  MN_LOSS_SMOOTH_L1 = 2, /* nn.SmoothL1Loss:  |d| < beta ? 0.5 d^2 / beta : |d| - 0.5 beta  (beta == 0: L1) */
+  MN_LOSS_HUBER = 3,     /* nn.HuberLoss:     |d| <= delta ? 0.5 d^2 : delta (|d| - 0.5 delta)        */
+  MN_LOSS_QUATERNION = 4 /* QuaternionLoss (common/criterion.py:15-31), rotation only: 1 - (p.g)^2 per row of three rotation
+                          * components, mean over rows */
+};
 
 const char* mn_last_error(void);
 /* "hip" for the product library; the test-only SIMT-emulator build reports "emu". */
@@ -132,6 +143,12 @@ void mn_destroy(mn_handle* h);
 /* Criterion log-weights live at params[param_floats-4 ..]; which of them Adam may update:
  * replaces `learn_beta` / `learn_gamma` (common/criterion.py:39-40,71-74; scripts/train.py:104-112) */
 int mn_set_learn_flags(mn_handle* h, int learn_beta, int learn_gamma);
+/* replaces the `t_loss_fn` / `q_loss_fn` constructor arguments of the criteria (common/criterion.py:34,55,112; attributes
+ * :37-38,69-70,129-130): enum mn_loss_kind and its parameter for the translation and for the rotation components of every term
+ * of the plan's criterion (absolute :48-51,85-91,159-163 and VO :99-105,174-180).  Governs mn_train_step, mn_train_forward_loss
+ * and mn_loss from the next call on; a new plan is L1 / L1.  Refused (mn_last_error): MN_LOSS_QUATERNION as t_kind, a negative
+ * (or NaN) parameter, an unknown kind. */
+int mn_set_loss_fn(mn_handle* h, int t_kind, float t_param, int q_kind, float q_param);
 
 /* replaces Optimizer(params, 'adam', base_lr, weight_decay, **kw) (common/optimizer.py:12-23)
  * and max_grad_norm (common/train.py:357-358) */
@@ -397,6 +414,12 @@ int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, int H, int W,
  * backward (common/criterion.py).  s: device fp32[4].  dpred/ds/vos_out may be NULL. */
 int mn_op_criterion(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss,
                     float* dpred, float* ds, float* vos_out, float grad_scale, void* stream);
+/* the same with the criterion's t_loss_fn / q_loss_fn (common/criterion.py:34,55,112) given as enum mn_loss_kind + parameter;
+ * mn_op_criterion is (MN_LOSS_L1, 0, MN_LOSS_L1, 0), the reference's defaults.  With MN_LOSS_QUATERNION (common/criterion.py:15-31)
+ * the rotation means run over rows of three components: d loss / d p = -2 (p.g) g / rows.  Refuses what mn_set_loss_fn refuses. */
+int mn_op_criterion_fn(int mode, int N, int T, const float* pred, const float* targ, const float* s, float* loss,
+                       float* dpred, float* ds, float* vos_out, float grad_scale, int t_kind, float t_param, int q_kind,
+                       float q_param, void* stream);
 /* replaces pose_utils.calc_vos (common/pose_utils.py:248-260) and its autograd VJP */
 int mn_op_calc_vos(const float* poses, int N, int T, float* vos, const float* cot, float* dposes, void* stream);
 

@@ -74,6 +74,15 @@ def build_parser():
                         help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
                              "transform, scripts/train.py:120): the dataset yields frames of --height x --width and the network runs "
                              "at the resized size; needs --u8_input")
+    kinds = ("l1", "mse", "smooth_l1", "huber", "quaternion")
+    parser.add_argument("--t_loss_fn", choices=kinds, default="l1",
+                        help="the training criterion's t_loss_fn (common/criterion.py:34,55,112; the reference's scripts pass "
+                             "none, i.e. nn.L1Loss): l1, mse, smooth_l1 (beta = --loss_param), huber (delta = --loss_param), all "
+                             "evaluated in the fused criterion kernel; quaternion is a rotation loss and is refused here")
+    parser.add_argument("--q_loss_fn", choices=kinds, default="l1",
+                        help="the training criterion's q_loss_fn: as --t_loss_fn, or quaternion (QuaternionLoss, "
+                             "common/criterion.py:15-31).  The validation criterion keeps L1 for both, as in the reference")
+    parser.add_argument("--loss_param", type=float, default=1.0, help="beta of smooth_l1 / delta of huber")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     parser.add_argument("--epochs", type=int, default=None, help="override [training] n_epochs")
@@ -175,11 +184,17 @@ def run(args, datasets=None, _binding=None, log=print):
         model.set_color_jitter(color_jitter, color_jitter, color_jitter, 0.5, seed=seed ^ (_rank() << 32))
 
     # loss function
+    def loss_module(name):
+        return {"l1": torch.nn.L1Loss, "mse": torch.nn.MSELoss, "quaternion": G.QuaternionLoss,
+                "smooth_l1": lambda: torch.nn.SmoothL1Loss(beta=args.loss_param),
+                "huber": lambda: torch.nn.HuberLoss(delta=args.loss_param)}[name]()
+
+    fkw = dict(t_loss_fn=loss_module(args.t_loss_fn), q_loss_fn=loss_module(args.q_loss_fn))
     if args.model == "posenet":
-        train_criterion = G.PoseNetCriterion(sax=sax, saq=saq, learn_beta=args.learn_beta, **kw)
+        train_criterion = G.PoseNetCriterion(sax=sax, saq=saq, learn_beta=args.learn_beta, **fkw, **kw)
         val_criterion = G.PoseNetCriterion(**kw)
     else:
-        ckw = dict(sax=sax, saq=saq, srx=srx, srq=srq, learn_beta=args.learn_beta, learn_gamma=args.learn_gamma, **kw)
+        ckw = dict(sax=sax, saq=saq, srx=srx, srq=srq, learn_beta=args.learn_beta, learn_gamma=args.learn_gamma, **fkw, **kw)
         if online:
             train_criterion = G.MapNetOnlineCriterion(gps_mode=(vo_lib == "gps"), **ckw)
             val_criterion = G.MapNetOnlineCriterion(**kw)
