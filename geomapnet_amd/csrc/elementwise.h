@@ -315,32 +315,26 @@ static __global__ void __launch_bounds__(256) bn_relu_maxpool_kernel(const T* __
   }
 }
 
-// N consecutive elements of type TY starting at element index `i * N` (N * sizeof(TY) = 16 or 32 bytes), read as floats
-template <typename TY, int N>
+// one 16-byte piece of the conv output, read as floats
+template <typename E>
 struct YVec {
-  static constexpr int PIECES = N * (int)sizeof(TY) / 16;
-  static constexpr int PER = 16 / (int)sizeof(TY);
-  PieceView<TY> v[PIECES];
-  __device__ __forceinline__ void load(const TY* __restrict__ base, long i) {
-#pragma unroll
-    for (int k = 0; k < PIECES; ++k) v[k].p = reinterpret_cast<const piece_t*>(base)[i * PIECES + k];
+  PieceView<E> v;
+  __device__ __forceinline__ void load(const E* __restrict__ base, long i) { v.p = reinterpret_cast<const piece_t*>(base)[i]; }
+  __device__ __forceinline__ void load_last(const E* __restrict__ base, long i) {
+    v.p = MN_LOAD_LAST(reinterpret_cast<const piece_t*>(base) + i);
   }
-  __device__ __forceinline__ void load_last(const TY* __restrict__ base, long i) {
-#pragma unroll
-    for (int k = 0; k < PIECES; ++k) v[k].p = MN_LOAD_LAST(reinterpret_cast<const piece_t*>(base) + i * PIECES + k);
-  }
-  __device__ __forceinline__ float at(int e) const { return (float)v[e / PER].e[e % PER]; }
+  __device__ __forceinline__ float at(int e) const { return (float)v.e[e]; }
 };
 
 // ---- BatchNorm backward ---------------------------------------------------------------------------
 // reduce: accum[0][c] += sum gm, accum[1][c] += sum gm * xhat,  gm = g * (gate > 0 if gate)
 // POOL: the gradient is gathered from (argmax, pooled gradient) -- a separate instantiation so that the common form does
 // not carry the gather's registers
-// TY (round 5, the fp16x2m mode): element type of the conv output y when it differs from the gradient's -- fp16 gradients against
-// the fp32 conv output of the split-operand forward pass (the self gate and xhat then come from the exact forward values)
-template <typename T, bool POOL = false, int U = 4, typename TY = T>
+// (the fp16x2m mode's fp16 gradients take the gate and xhat from the forward pass's record instead: elementwise_h2.h,
+// launch_bn_bwd_rec)
+template <typename T, bool POOL = false, int U = 4>
 static __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict__ g, const T* __restrict__ gate,
-                                                             const TY* __restrict__ y, const float* __restrict__ mean,
+                                                             const T* __restrict__ y, const float* __restrict__ mean,
                                                              const float* __restrict__ invstd, long M, int C,
                                                              double* __restrict__ accum, int rows_per_block,
                                                              float* __restrict__ partial,
@@ -369,7 +363,7 @@ static __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __re
   // U rows per iteration, all loads issued before the arithmetic (memory-level parallelism)
   for (long r = r0 + rl; r < r1; r += (long)U * rlanes) {
     PieceView<T> vg[U], vm[U];
-    YVec<TY, VEC> vy[U];
+    YVec<T> vy[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long rr = r + (long)u * rlanes;
@@ -519,9 +513,9 @@ static __global__ void __launch_bounds__(256) bn_finalize_bwd_kernel(const doubl
 }
 
 // apply: gy = k1 * (gm - mg - xhat * mgx)
-template <typename T, bool POOL = false, typename TY = T>
+template <typename T, bool POOL = false>
 static __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__ g, const T* __restrict__ gate,
-                                                            const TY* __restrict__ y, const float* __restrict__ mean,
+                                                            const T* __restrict__ y, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd, const float* __restrict__ coef,
                                                             T* __restrict__ gy, long npieces, int C, int self_gate,
                                                             PoolGradSrc pg) {
@@ -557,7 +551,7 @@ static __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __res
   // tails are what the caches still hold -- was measured: no gain.)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npieces; i += (long)gridDim.x * blockDim.x) {
     PieceView<T> vg, vm, o;
-    YVec<TY, VEC> vy;
+    YVec<T> vy;
     if constexpr (POOL) {
       float a[VEC];
       const long row = i / cpr;
@@ -628,8 +622,8 @@ static __global__ void __launch_bounds__(256) bn_fwd_stats_kernel(const T* __res
 
 // BatchNorm backward = reduce -> finalize -> apply.  accum: [accum_rows][2][C] doubles, zero on entry (left holding the
 // sums); coef: [4][C] floats of scratch ([3][C] without the self gate).
-template <typename T, typename TY = T>
-inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C, const float* gamma, const float* mean,
+template <typename T>
+inline void launch_bn_bwd(const T* g, const T* gate, const T* y, long M, int C, const float* gamma, const float* mean,
                           const float* invstd, float* dgamma, float* dbeta, T* gy, double* accum, float* coef,
                           float grad_unscale, hipStream_t s, const float* self_gate_beta = nullptr,
                           PoolGradSrc pg = PoolGradSrc(), int accum_rows = 1, bool apply = true) {
@@ -656,7 +650,7 @@ inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C,
   // rows in flight per thread: 2 for fp16 tensors (111 instead of 122 registers: one more wave fits beside the side stream's
   // weight gradient; 14.01 -> 13.89 ms per step), 4 for fp32 tensors (2: 30.74 -> 30.88 ms in the fp16x2 mode); profiles/r04/c11_*
   // the stem on fp32 tensors: sums in pooled-window order (profiles/r04/c32_stem_bn_sums_window_order_fp32.txt)
-  if (pg.idx && sizeof(T) == 4 && sizeof(TY) == 4 && self_gate_beta) {
+  if (pg.idx && sizeof(T) == 4 && self_gate_beta) {
     const long nwin = (long)(M / ((long)pg.H * pg.W)) * pg.Po * pg.Qo;
     long wrows = (nwin + target - 1) / target;
     wrows = ((wrows + rlanes - 1) / rlanes) * rlanes;
@@ -668,10 +662,10 @@ inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C,
   // (s_setprio 3 in the backward kernels, so that their waves are not starved by the weight gradient's MFMA waves on the same
   //  SIMD: no effect, 13.95 vs 14.00 ms fp16, 30.36 vs 30.38 ms fp16x2, profiles/r04/c12_*; removed)
   if (pg.idx)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, 4, TY>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, 4>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
                        rows_per_block, (float*)nullptr, sg_gamma, self_gate_beta, pg, accum_rows);
   else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, reduce_u, TY>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, reduce_u>), dim3(nblk), dim3(256), 0, s, g, gate, y, mean, invstd, M, C, accum,
                        rows_per_block, (float*)nullptr, sg_gamma, self_gate_beta, pg, accum_rows);
   }
 #ifdef MN_ABLATION_BUILD
@@ -686,10 +680,10 @@ inline void launch_bn_bwd(const T* g, const T* gate, const TY* y, long M, int C,
   if (!apply) return;
   long np = M * C / VEC;
   if (pg.idx)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, TY>), dim3(ew_grid(np)), dim3(256), 0, s, g, gate, y, mean, invstd,
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(ew_grid(np)), dim3(256), 0, s, g, gate, y, mean, invstd,
                        (const float*)coef, gy, np, C, self_gate_beta ? 1 : 0, pg);
   else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, TY>), dim3(ew_grid(np)), dim3(256), 0, s, g, gate, y, mean, invstd,
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(ew_grid(np)), dim3(256), 0, s, g, gate, y, mean, invstd,
                        (const float*)coef, gy, np, C, self_gate_beta ? 1 : 0, pg);
 }
 

@@ -193,6 +193,9 @@ struct PlanBase {
   virtual void after_optim_host() = 0;
   virtual int sync_step_to_device(hipStream_t s) = 0;
   virtual int64_t applied_steps() = 0;  // the device's count of optimiser steps that were applied (waits for the device)
+  virtual size_t carve(char* base) = 0;  // lay the work arena out from `base` (null: only measure it); returns its bytes
+  virtual int attach(float* params, float* opt_state, void* buffers, void* work, hipStream_t s) = 0;
+  virtual void update_frozen(hipStream_t s) = 0;
   virtual int forward(const void* images, float* poses_out, int training, hipStream_t s) = 0;
   // dropout between the feature vector's ReLU and the pose heads (mn_set_dropout): probability, Philox key, calls so far
   float drop_p = 0.f;
@@ -228,8 +231,7 @@ struct PlanBase {
   // newly seen skip halves the scale, `scale_growth_interval` clean steps double it (0 = never grow).  The host reacts
   // one or two steps late; until then the device keeps skipping, so no non-finite value reaches weights or moments.
   float cur_scale = 1.f;
-  bool overflow_guard = false;
-  long long* overflow_host = nullptr;  // pinned: {last step skipped, skipped steps in total, last skipped attempt, last COMPLETED attempt}
+  long long* overflow_host = nullptr;  // (only plans that guard against overflow allocate it) pinned: {last step skipped, skipped steps in total, last skipped attempt, last COMPLETED attempt}
   long long skipped_seen = 0;
   long long done_seen = 0;        // last completed attempt the host has accounted for (overflow_host[3])
   int64_t attempts = 0;           // optimiser steps enqueued on this plan (skipped ones included)
@@ -245,7 +247,7 @@ struct PlanBase {
   // with "nothing finished yet" could reset the counter forever and silently train nothing, and the loss scale grew on polls
   // that observed nothing.)
   void poll_overflow() {
-    if (!overflow_guard || !overflow_host) return;
+    if (!overflow_host) return;
     const long long done = *(volatile long long*)(overflow_host + 3);   // read first: a copy landing in between can only make
     const long long seen = *(volatile long long*)(overflow_host + 1);   // `seen` newer than `done` (fewer clean steps counted)
     const long long last_bad = *(volatile long long*)(overflow_host + 2);
@@ -299,6 +301,92 @@ struct Plan : PlanBase {
   static constexpr int VEC = ElemTraits<T>::VEC;
   static constexpr int DT = ElemTraits<T>::DTYPE;
 
+  // ---- the mode ---------------------------------------------------------------------------------
+  // What cfg.dtype (and MN_DETERMINISTIC) means for this plan, stated once: mode_of() fills it, carve, the launch helpers and
+  // debug_tensor read it, and nothing else asks for the dtype.  A format is the MN_DTYPE_* code mn_debug_tensor reports.  The
+  // arena is carved in elements of T whatever the format: an h2 / h2q element takes 4 bytes like fp32, and the plain fp16 tensors of
+  // the fp16x2m backward pass sit in the buffers carved for fp32 -- the T* members below hold what `md` says, and the launches cast.
+  static constexpr int FMT_F32 = MN_DTYPE_F32, FMT_F16 = MN_DTYPE_F16, FMT_H2 = MN_DTYPE_F16X2, FMT_H2Q = MN_DTYPE_F16X2Q;
+  // the stem's backward pass: the two tile-walking fp16 kernels of stem_bwd.h on the stem's own tensors (fp16), the same kernels on
+  // fp16 COPIES of the fp32 conv output and of the padded input (fp16x2m), or the chain BatchNorm backward -> weight gradient
+  enum StemBwd { STEM_TILES, STEM_TILES_ON_COPIES, STEM_CHAIN };
+  struct Mode {
+    int act;     // activations a convolution consumes: block inputs / outputs, a1, the projection output, the pooled stem output
+    int y;       // raw conv outputs (and everything of the stem but its pooled output): always T
+    int gy;      // d(conv output)
+    int gx;      // data gradients: ga1, gout, gp0
+    int wf, wd;  // forward / data-gradient weight copies (wf = FMT_F32: no copy, the OHWI master is the operand)
+    int mma_fwd, mma_bwd;  // contraction of the kernels that read fp32 tensors (common.h MMA_*)
+    StemBwd stem_bwd;
+    bool overflow_guard;  // gradients pass through fp16: scale the loss, skip overflowed steps (PlanBase::poll_overflow)
+    bool pairs() const { return act == FMT_H2 || act == FMT_H2Q; }    // the h2 forward pass
+    bool f16_bwd_on_pairs() const { return pairs() && gy == FMT_F16; }  // ... with the fp16 mode's backward kernels behind it
+  };
+  static Mode mode_of(int dtype, bool deterministic) {
+    Mode m;
+    m.act = m.y = m.gy = m.gx = m.wf = m.wd = DT;  // MN_DTYPE_F32, MN_DTYPE_F16 (which copies its weights: Plan<half> only)
+    m.mma_fwd = m.mma_bwd = MMA_NATIVE;
+    m.overflow_guard = DT == MN_F16;
+    // (MN_DETERMINISTIC: the stem's backward goes through BatchNorm backward + the split-slice weight gradient instead)
+    m.stem_bwd = DT == MN_F16 && !deterministic ? STEM_TILES : STEM_CHAIN;
+    if (DT == MN_F16 || dtype == MN_DTYPE_F32) return m;
+    // MN_DTYPE_F32X3 (Plan<float> only): fp32 tensors, contractions on the f16 / bf16 matrix pipe with split operands
+    // (common.h MMA_*): forward f16x3, backward bf16x3; the fc / pose head stay on the exact fp32 MFMA
+    m.mma_fwd = MMA_F16X3;  // (the h2 modes too: the stem's kernels and its fp32 tensors)
+    m.mma_bwd = MMA_BF16X3;
+    if (dtype == MN_DTYPE_F32X3) return m;
+    // MN_DTYPE_F16X2 (Plan<float> only): every tensor a convolution consumes -- block inputs / outputs, a1, the projection
+    // output, d(conv output), both weight copies -- is an h2 tensor (fp16 hi + lo halves, 4 bytes per element: the arena is
+    // carved exactly as for fp32), written by the h2 element-wise kernels (elementwise_h2.h) and read by the h2 convolution
+    // kernels through LDS-DMA; raw conv outputs, data gradients, statistics, head, criterion and optimiser are fp32.  The stem
+    // (3 input channels: no 32-channel groups) stays on the fp32x3 kernels: fp32 xpad / stem.gy, f16x3 / bf16x3 contraction.
+    // Gradients live in fp16 pairs, so the mode scales the loss and guards against overflow exactly as the fp16 mode does.
+    m.act = m.gy = m.wf = m.wd = FMT_H2;
+    m.overflow_guard = true;
+    if (dtype == MN_DTYPE_F16X2) return m;
+    // MN_DTYPE_F16X2M (round 5; Plan<float> only): the fp16x2 FORWARD pass, bit for bit -- loss and poses are that mode's -- and a
+    // backward pass that contracts SINGLE fp16 operands, one MFMA per product, on the fp16 mode's kernels: d(conv output), data
+    // gradients and the data-gradient weight copy are plain fp16 tensors (in the buffers the arena carves for fp32); the X operand of
+    // a weight gradient and the ReLU gates are the HI halves of the h2 activations, read in place (round 5 read plain fp16 COPIES
+    // written beside the h2 tensors; round 6: WgradArgs::x_h2, Epilogue::gate_h2 -- 2 bytes per activation element less written by
+    // every BatchNorm apply, 2.5 GB less arena at 192 images).
+    // What stays exact: every gate (sign of the forward value) and BatchNorm's backward statistics (fp32 conv output, fp64 sums).
+    // What it costs the gradients: 1.1e-3 relative L2 overall / 1.6e-3 worst tensor (tools/mixed_budget.py: the oracle's own step
+    // with fp16 conv operands in the backward pass) -- a fifth of the 4.9e-3 / 1.1e-2 by which two correct fp32 evaluations of this
+    // network differ through ReLU gate flips.  The STEM is the exception to "statistics from the exact forward
+    // values": by default (STEM_TILES_ON_COPIES) its two backward kernels (stem_bwd.h) read an fp16 copy of the fp32 conv output
+    // (written by the stem's BatchNorm + max-pool pass) and an fp16 image of the input, so its BatchNorm-backward sums and xhat come
+    // from fp16-rounded y; only its ReLU gate stays exact (the pooled gradient arrives already gated by layer1.0's data gradient:
+    // StemBwdArgs::pre_gated).  MN_DETERMINISTIC=1 keeps the fp32 chain of fp16x2 for the stem.
+    // Round 6: BatchNorm's backward pass reads a 2-byte RECORD of the forward pass (fp16 xhat + the ReLU's outcome in its lowest
+    // bit, written by the forward apply) instead of the 4-byte conv output -- 2 bytes per element more in one forward pass, 2 fewer
+    // in each of the two backward passes, and the gate stays exact (Unit::rec; profiles/r06/c4_batchnorm_backward_from_a_record.txt).
+    m.gy = m.gx = m.wd = FMT_F16;
+    if (!deterministic) m.stem_bwd = STEM_TILES_ON_COPIES;
+    // MN_DTYPE_F16X2Q (round 5; Plan<float> only): fp16x2m whose FORWARD convolutions take both cross terms of a split-operand
+    // product from fp8 copies on the block-scaled MFMA (common.h MMA_H2Q, h2q tensors): 2 instead of 3 MFMA-equivalents per forward
+    // product, poses ~3e-4 from the fp32 reference instead of 1.6e-5 (bar 1e-3)
+    if (dtype == MN_DTYPE_F16X2Q) m.act = m.wf = FMT_H2Q;
+    return m;
+  }
+  // MN_DETERMINISTIC=1: bit-reproducible training steps -- every floating-point sum the step takes is added in an order
+  // that does not depend on scheduling: BatchNorm sums through one accumulator row per producing workgroup (carve),
+  // weight gradients through per-split workspace slices and an ordered reduction (conv_wgrad), the gradient norm through
+  // per-workgroup partial sums (optim.h).  Costs ~x ms per step (DESIGN.md section 4).
+  const bool deterministic = knobs().deterministic;
+  const Mode md;
+  // ---- schedule knobs (knobs.h), copied at construction -------------------------------------------------------------
+  // bit 0: BatchNorm+ReLU+max-pool in one forward pass (-0.15 ms/step); bit 1: max-pool gradient gathered inside the
+  // BatchNorm backward passes instead of a maxpool_bwd launch (measured +0.05 ms/step: the gather runs twice) -- off
+  const int fuse_stem_mask = knobs().fuse_stem;
+  const bool fuse_stem = (fuse_stem_mask & 1) != 0;
+  const bool fuse_stem_bwd = (fuse_stem_mask & 2) != 0;
+  static constexpr bool parity_dgrad = true;  // stride-2 data gradients by parity class (dgrad.h: -1.6 % step time)
+  // Weight-gradient schedule: the knobs, the per-mode defaults and their measurements are in knobs.h (resolve_wgrad_schedule)
+  const WgradSchedule wgrad = resolve_wgrad_schedule(knobs(), md.overflow_guard, md.gy == FMT_F16);
+  const int wgrad_tail = knobs().wgrad_tail;
+
+  // ---- the network: units, blocks and their places in the arenas ---------------------------------------------------------
   struct Unit {  // conv + BatchNorm
     ConvP cp;
     BnP bp;
@@ -306,10 +394,10 @@ struct Plan : PlanBase {
     long M;
     GatherGeom gf;
     DgradGeom dg;  // data-gradient launches (generic form + stride-2 parity classes), dgrad.h
-    T* wf = nullptr;  // forward operand  [Cout][K]
-    T* wd = nullptr;  // data-gradient operand [Cin][R*S*Cout]
+    T* wf = nullptr;  // forward operand  [Cout][K], format md.wf
+    T* wd = nullptr;  // data-gradient operand [Cin][R*S*Cout], format md.wd
     T* y = nullptr;   // raw conv output [M][Cout]
-    T* gy = nullptr;  // its gradient
+    T* gy = nullptr;  // its gradient, format md.gy
     half* rec = nullptr;  // fp16x2m: the BatchNorm's backward record [M][Cout] (elementwise_h2.h rec_pack), written by the forward apply
     float *mean, *invstd;
     float *coef_f, *coef_b;  // per-channel coefficients of the forward apply [2][C] / backward apply [4][C] (finalize kernels)
@@ -318,7 +406,7 @@ struct Plan : PlanBase {
     int ldw;           // row pitch of the master weight gradient
     const int* colmap = nullptr;
   };
-  struct Block {
+  struct Block {  // activations in format md.act, their gradients in md.gx
     Unit u1, u2, ud;
     bool down;
     int stage;
@@ -329,9 +417,6 @@ struct Plan : PlanBase {
     T* zd;        // bn_d(conv_d x) when down
     T* out;       // block output
     T* gout;      // gradient w.r.t. block output (written by the consumer)
-    // (fp16x2m, round 5: plain fp16 COPIES of the h2 activations fed the single-fp16 backward pass; round 6: its kernels read the hi
-    //  halves of the h2 tensors themselves -- WgradArgs::x_h2, Epilogue::gate_h2 -- and the copies are gone: 2 bytes per activation
-    //  element less written by every BatchNorm apply, 2.5 GB less arena at 192 images)
   };
 
   float *params, *grads, *m1, *m2;
@@ -352,24 +437,16 @@ struct Plan : PlanBase {
   // BatchNorm sums are accumulated with fp64 atomics straight from the producing kernels (conv epilogue, backward
   // reduction) into ACC_ROWS rows per unit (row = producer block % ACC_ROWS, to spread same-address contention);
   // the consuming apply kernels add the rows in their prologue.  No separate partial-reduction launches.
-  // MN_DETERMINISTIC=1: bit-reproducible training steps -- every floating-point sum the step takes is added in an order
-  // that does not depend on scheduling: BatchNorm sums through one accumulator row per producing workgroup (below),
-  // weight gradients through per-split workspace slices and an ordered reduction (conv_wgrad), the gradient norm through
-  // per-workgroup partial sums (optim.h).  Costs ~x ms per step (DESIGN.md section 4).
-  const bool deterministic = knobs().deterministic;
   static constexpr int ACC_ROWS = 8;  // (32 rows measured equal: 14.73 vs 14.69 ms per step)
   double* acc_region = nullptr;
   size_t acc_bytes = 0;
-  int cur_training = 1;
   double* sqnorm;             // squared gradient norm: the first double of acc_region
-  bool sqnorm_clean = false;  // zeroed by this step's fill and not yet accumulated into
   static constexpr int kSqPartials = 8192;
   double* sq_partials = nullptr;  // MN_DETERMINISTIC: per-workgroup sums of the gradient norm
   unsigned char* frozen;
   int* stem_colmap;
   RepackJob* repack_jobs;
   int repack_njobs = 0, repack_blocks = 0, repack_head_jobs = -1, repack_head_blocks = 0;
-  bool grads_zeroed = false;
   unsigned char* pool_idx;  // winning tap of every max-pool window
   float* wgf_ws = nullptr;  // partial tiles of the fused weight gradient (wgrad_fused.h), shared by its launches (one stream)
   long wgf_ws_floats = 0;
@@ -377,39 +454,48 @@ struct Plan : PlanBase {
   long long* overflow_dev;  // {this step skipped, skipped steps in total, last skipped attempt, last completed attempt} (adam_prep_kernel)
   long long* step_dev;      // device-resident Adam step counter
   float* bc_dev;            // {1 - beta1^t, 1 - beta2^t}, derived on device from step_dev
+
+  // ---- state of the step being enqueued ------------------------------------------------------------------------------
+  int cur_training = 1;
+  bool sqnorm_clean = false;  // zeroed by this step's fill and not yet accumulated into
+  bool grads_zeroed = false;
   const float* cur_targets = nullptr;
   float* cur_loss = nullptr;
+  struct PendingWgrad {
+    Unit* u;
+    const T* x;
+  };
+  std::vector<PendingWgrad> pending_wgrads;  // weight gradients held back until the next fork (flush_wgrads)
 
   // ---- construction -----------------------------------------------------------------------
-  size_t carve(char* base) {
+  size_t carve(char* base) override {
     Bump b;
     auto A = [&](size_t bytes) { return base ? base + b.take(bytes) : (b.take(bytes), (char*)nullptr); };
     // all BatchNorm accumulators live in one region so a single memset per step clears them
-    auto set_rows = [&](Unit& u, bool is_stem) {
+    // MN_DETERMINISTIC: one row per producing workgroup: every (row, channel) slot then receives exactly ONE atomic add onto zero,
+    // and the finalize kernels add the rows in a fixed order.  Forward producers: the stem kernel's persistent workgroups, the
+    // layer1 kernel's persistent workgroups (halo_pp.h: at most one per 16x16-pixel tile), M-tiles of >= 128 rows elsewhere.
+    auto set_rows = [&](Unit& u) {
       u.rows_f = u.rows_b = ACC_ROWS;
       if (!deterministic) return;
-      // one row per producing workgroup: every (row, channel) slot then receives exactly ONE atomic add onto zero, and the
-      // finalize kernels add the rows in a fixed order.  Forward producers: the stem kernel's persistent workgroups, the
-      // layer1 kernel's persistent workgroups (halo_pp.h: at most one per 16x16-pixel tile), M-tiles of >= 128 rows elsewhere.
-      if (is_stem)
-        u.rows_f = (DT == MN_F16 || mma_fwd == MMA_F16X3) ? 1024 : cdiv((int)u.M, 128);
-      else if (halo_path(u.gf))
-        u.rows_f = u.gf.B * cdiv(u.gf.P, kHaloTH) * cdiv(u.gf.Q, kHaloTW);
-      else
-        u.rows_f = cdiv((int)u.M, 128);
+      u.rows_f = halo_path(u.gf) ? u.gf.B * cdiv(u.gf.P, kHaloTH) * cdiv(u.gf.Q, kHaloTW) : cdiv((int)u.M, 128);
       // (layer1's h2 convolutions on the persistent register-resident-weight kernel, halo_h2.h: one row per workgroup)
-      if (h2 && !q8 && !is_stem && u.cp.k == 3 && u.cp.stride == 1 && u.cp.cin == 64 && u.cp.cout == 64) {
+      if (md.act == FMT_H2 && u.cp.k == 3 && u.cp.stride == 1 && u.cp.cin == 64 && u.cp.cout == 64) {
         const int wgs = conv_halo_h2_grid(u.gf);
         if (u.rows_f < wgs) u.rows_f = wgs;
       }
       u.rows_b = 1024;  // >= the workgroups of a backward reduction (launch_bn_bwd: ~512)
     };
-    set_rows(stem, true);
+    stem.rows_f = stem.rows_b = ACC_ROWS;
+    if (deterministic) {
+      stem.rows_f = (DT == MN_F16 || md.mma_fwd == MMA_F16X3) ? 1024 : cdiv((int)stem.M, 128);
+      stem.rows_b = 1024;
+    }
     size_t acc_doubles = (size_t)(stem.rows_f + stem.rows_b) * 2 * 64;
     for (auto& blk : blocks) {
-      set_rows(blk.u1, false);
-      set_rows(blk.u2, false);
-      if (blk.down) set_rows(blk.ud, false);
+      set_rows(blk.u1);
+      set_rows(blk.u2);
+      if (blk.down) set_rows(blk.ud);
       acc_doubles += (size_t)(blk.u1.rows_f + blk.u1.rows_b + blk.u2.rows_f + blk.u2.rows_b) * 2 * blk.u1.cp.cout;
       if (blk.down) acc_doubles += (size_t)(blk.ud.rows_f + blk.ud.rows_b) * 2 * blk.ud.cp.cout;
     }
@@ -441,7 +527,7 @@ struct Plan : PlanBase {
     p0 = (T*)A(n1 * sizeof(T));
     gp0 = (T*)A(n1 * sizeof(T));
     pool_idx = (unsigned char*)A(n1);
-    if (mixed) xpad16 = (half*)A((size_t)B * Hp * Wp * 4 * sizeof(half));
+    if (md.f16_bwd_on_pairs()) xpad16 = (half*)A((size_t)B * Hp * Wp * 4 * sizeof(half));
     const T* x = p0;
     T* gx = gp0;
     for (auto& blk : blocks) {
@@ -451,9 +537,9 @@ struct Plan : PlanBase {
       for (Unit* u : us) {
         if (!u) continue;
         unit_bufs(*u);
-        if (mixed) u->rec = (half*)A((size_t)u->M * u->cp.cout * sizeof(half));
+        if (md.f16_bwd_on_pairs()) u->rec = (half*)A((size_t)u->M * u->cp.cout * sizeof(half));
         size_t wn = (size_t)u->cp.cout * u->cp.cin * u->cp.k * u->cp.k;
-        if (DT == MN_F16 || h2)
+        if (md.wf != FMT_F32)
           u->wf = (T*)A(wn * sizeof(T));  // (h2: 4 bytes per element as well)
         else
           u->wf = base ? (T*)(params + u->cp.w) : nullptr;  // fp32: the OHWI master is the operand
@@ -483,7 +569,7 @@ struct Plan : PlanBase {
     stem_colmap = (int*)A(224 * 4);
     repack_jobs = (RepackJob*)A(64 * sizeof(RepackJob));
     zero_page = (void*)A(256);
-    wgf_ws_floats = (DT == MN_F16 || mma_bwd == MMA_BF16X3) ? wgrad_fused_ws_floats(WGF_BLOCKS) : 0;  // (all fused forms)
+    wgf_ws_floats = (DT == MN_F16 || md.mma_bwd == MMA_BF16X3) ? wgrad_fused_ws_floats(WGF_BLOCKS) : 0;  // (all fused forms)
     if (deterministic && wgf_ws_floats < (16L << 20)) wgf_ws_floats = 16L << 20;  // split slices of the plain weight gradients
     wgf_ws = wgf_ws_floats ? (float*)A((size_t)wgf_ws_floats * 4) : nullptr;
     step_dev = (long long*)A(256);
@@ -515,58 +601,14 @@ struct Plan : PlanBase {
     u.gf = fwd_geom(B, Hin, Win, c, u.Hout, u.Wout);
     u.ldw = c.k * c.k * c.cin;
     u.dg = make_dgrad_geom(B, Hin, Win, c.cin, c.cout, c.k, c.stride, c.pad, u.Hout, u.Wout, VEC);
-    u.gf.mma = mma_fwd;
-    u.dg.full.mma = mma_bwd;
-    for (int i = 0; i < u.dg.n_pc; ++i) u.dg.pc[i].g.mma = mma_bwd;
+    u.gf.mma = md.mma_fwd;
+    u.dg.full.mma = md.mma_bwd;
+    for (int i = 0; i < u.dg.n_pc; ++i) u.dg.pc[i].g.mma = md.mma_bwd;
   }
 
-  // MN_DTYPE_F32X3 (Plan<float> only): fp32 tensors, contractions on the f16 / bf16 matrix pipe with split operands
-  // (common.h MMA_*): forward f16x3, backward bf16x3; the fc / pose head stay on the exact fp32 MFMA
-  int mma_fwd = MMA_NATIVE, mma_bwd = MMA_NATIVE;
-  // MN_DTYPE_F16X2 (Plan<float> only): every tensor a convolution consumes -- block inputs / outputs, a1, the projection
-  // output, d(conv output), both weight copies -- is an h2 tensor (fp16 hi + lo halves, 4 bytes per element: the arena is
-  // carved exactly as for fp32), written by the h2 element-wise kernels (elementwise_h2.h) and read by the h2 convolution
-  // kernels through LDS-DMA; raw conv outputs, data gradients, statistics, head, criterion and optimiser are fp32.  The stem
-  // (3 input channels: no 32-channel groups) stays on the fp32x3 kernels: fp32 xpad / stem.gy, f16x3 / bf16x3 contraction.
-  // Gradients live in fp16 pairs, so the mode scales the loss and guards against overflow exactly as the fp16 mode does.
-  bool h2 = false;
-  // MN_DTYPE_F16X2M (round 5; Plan<float> only): the fp16x2 FORWARD pass, bit for bit -- loss and poses are that mode's -- and a
-  // backward pass that contracts SINGLE fp16 operands, one MFMA per product, on the fp16 mode's kernels: d(conv output), data
-  // gradients and the data-gradient weight copy are plain fp16 tensors (in the buffers the arena carves for fp32), the X operand of
-  // a weight gradient and the ReLU gates read plain fp16 COPIES of the activations that the h2 producers write beside the h2 tensor.
-  // What stays exact: every gate (sign of the forward value) and BatchNorm's backward statistics (fp32 conv output, fp64 sums).
-  // What it costs the gradients: 1.1e-3 relative L2 overall / 1.6e-3 worst tensor (tools/mixed_budget.py: the oracle's own step
-  // with fp16 conv operands in the backward pass) -- a fifth of the 4.9e-3 / 1.1e-2 by which two correct fp32 evaluations of this
-  // network differ through ReLU gate flips.  The STEM is the exception to "statistics from the exact forward
-  // values": by default (stem_f16) its two backward kernels (stem_bwd.h) read an fp16 copy of the fp32 conv output (written by the
-  // stem's BatchNorm + max-pool pass) and an fp16 image of the input, so its BatchNorm-backward sums and xhat come from fp16-rounded
-  // y; only its ReLU gate stays exact (the pooled gradient arrives already gated by layer1.0's data gradient).  MN_DETERMINISTIC=1
-  // keeps the fp32 chain of fp16x2 for the stem.
-  bool mixed = false;
-  // fp16x2m, round 6: BatchNorm's backward pass reads a 2-byte RECORD of the forward pass (fp16 xhat + the ReLU's outcome in its
-  // lowest bit, written by the forward apply) instead of the 4-byte conv output -- 2 bytes per element more in one forward pass, 2
-  // fewer in each of the two backward passes, and the gate stays exact (Unit::rec; profiles/r06/c4_batchnorm_backward_from_a_record.txt).
-  // MN_DTYPE_F16X2Q (round 5; Plan<float> only): fp16x2m whose FORWARD convolutions take both cross terms of a split-operand product
-  // from fp8 copies on the block-scaled MFMA (common.h MMA_H2Q, h2q tensors): 2 instead of 3 MFMA-equivalents per forward product,
-  // poses ~3e-4 from the fp32 reference instead of 1.6e-5 (bar 1e-3)
-  bool q8 = false;
-  std::string stage_error;  // set by a launch helper of a backward stage that cannot return a status itself
-  Plan(const mn_config& c) {
+  Plan(const mn_config& c) : md(mode_of(c.dtype, knobs().deterministic)) {
     cfg = c;
     cur_scale = c.loss_scale;
-    q8 = DT == MN_F32 && c.dtype == MN_DTYPE_F16X2Q;
-    mixed = DT == MN_F32 && (c.dtype == MN_DTYPE_F16X2M || q8);
-    h2 = DT == MN_F32 && (c.dtype == MN_DTYPE_F16X2 || mixed);
-    stem_f16 = mixed && !deterministic;
-    if (c.dtype == MN_DTYPE_F32X3 || h2) {  // (fp16x2m: the stem's backward and its fp32 tensors)
-      mma_fwd = MMA_F16X3;
-      mma_bwd = MMA_BF16X3;
-    }
-    overflow_guard = DT == MN_F16 || h2;
-    const WgradSchedule ws = resolve_wgrad_schedule(knobs(), h2 || DT == MN_F16, mixed || DT == MN_F16);
-    wgrad_sched = ws.sched;
-    wgrad_early_stages = ws.early_stages;
-    wgrad_defer_stages = ws.defer_stages;
     L = Layout(c.feat_dim);
     frames = (c.mode == MN_MODE_POSENET) ? 1 : (c.mode == MN_MODE_MAPNET ? c.T : 2 * c.T);
     B = c.windows * frames;
@@ -585,7 +627,7 @@ struct Plan : PlanBase {
     g.B = B; g.Hi = Hp; g.Wi = Wp / 2; g.C = 8; g.P = H0; g.Q = W0; g.R = 7; g.S = 4;
     g.mul_p = 2; g.mul_q = 1; g.rsign = 1; g.ssign = 1; g.off_h = 0; g.off_w = 0; g.div = 1;
     g.M = B * H0 * W0; g.N = 64; g.K = 224;
-    g.mma = mma_fwd;
+    g.mma = md.mma_fwd;
     stem.gf = g;
     stem.ldw = 147;
     H1 = (H0 + 2 - 3) / 2 + 1;
@@ -606,7 +648,7 @@ struct Plan : PlanBase {
     Wl = w;
   }
 
-  int attach(float* params_, float* opt_state, void* buffers_, void* work_, hipStream_t s) {
+  int attach(float* params_, float* opt_state, void* buffers_, void* work_, hipStream_t s) override {
     params = params_;
     grads = opt_state;
     m1 = opt_state + L.param_floats;
@@ -626,7 +668,7 @@ struct Plan : PlanBase {
     hipMemcpyAsync(stem_colmap, cm.data(), 224 * 4, hipMemcpyHostToDevice, s);
     hipStreamSynchronize(s);  // cm is a host temporary
     stem.colmap = stem_colmap;
-    if (overflow_guard && !overflow_host) {
+    if (md.overflow_guard && !overflow_host) {
       if (hipHostMalloc((void**)&overflow_host, 4 * sizeof(long long)) != hipSuccess) {
         overflow_host = nullptr;
         (void)hipGetLastError();
@@ -640,7 +682,7 @@ struct Plan : PlanBase {
     return check_launch("attach");
   }
 
-  void update_frozen(hipStream_t s) {
+  void update_frozen(hipStream_t s) override {
     unsigned char f[4] = {(unsigned char)!learn_beta, (unsigned char)!learn_beta, (unsigned char)!learn_gamma,
                           (unsigned char)!learn_gamma};
     hipMemcpyAsync(frozen, f, 4, hipMemcpyHostToDevice, s);
@@ -671,7 +713,7 @@ struct Plan : PlanBase {
       for (Unit* u : us) {
         if (!u) continue;
         const ConvP& c = u->cp;
-        add(c.w, (DT == MN_F16 || h2) ? (void*)u->wf : nullptr, u->wd, c.cout, c.k, c.k, c.cin, 0);
+        add(c.w, md.wf != FMT_F32 ? (void*)u->wf : nullptr, u->wd, c.cout, c.k, c.k, c.cin, 0);
       }
     }
     add(L.fc_w, fcT, nullptr, cfg.feat_dim, 1, 1, 512, 3);
@@ -683,52 +725,27 @@ struct Plan : PlanBase {
   // head = stem + layer1 weights (needed first), tail = everything else; the tail can run on the side stream
   // while the stem and layer1 execute
   void repack_head(hipStream_t s) {
-    const int hj = repack_head_jobs > 0 ? repack_head_jobs : repack_njobs;
-    const int hb = repack_head_jobs > 0 ? repack_head_blocks : repack_blocks;
-    if constexpr (DT == MN_F32) {
-      if (q8) {  // forward operand h2q, data-gradient operand plain fp16
-        hipLaunchKernelGGL((repack_all_kernel<float, true, true, true>), dim3(hb), dim3(256), 0, s, (const RepackJob*)repack_jobs, hj,
-                           (const float*)params, 0);
-        return;
-      }
-      if (mixed) {  // forward operand h2, data-gradient operand plain fp16
-        hipLaunchKernelGGL((repack_all_kernel<float, true, true>), dim3(hb), dim3(256), 0, s, (const RepackJob*)repack_jobs, hj,
-                           (const float*)params, 0);
-        return;
-      }
-      if (h2) {
-        hipLaunchKernelGGL((repack_all_kernel<float, true>), dim3(hb), dim3(256), 0, s, (const RepackJob*)repack_jobs, hj,
-                           (const float*)params, 0);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((repack_all_kernel<T>), dim3(hb), dim3(256), 0, s, (const RepackJob*)repack_jobs, hj,
-                       (const float*)params, 0);
+    const bool split = repack_head_jobs > 0;
+    launch_repack(0, split ? repack_head_blocks : repack_blocks, split ? repack_head_jobs : repack_njobs, s);
   }
   void repack_tail(hipStream_t s) {
     const int hb = repack_head_jobs > 0 ? repack_head_blocks : repack_blocks;
-    if (repack_blocks > hb) {
-      bool done = false;
-      if constexpr (DT == MN_F32) {
-        if (q8) {
-          hipLaunchKernelGGL((repack_all_kernel<float, true, true, true>), dim3(repack_blocks - hb), dim3(256), 0, s,
-                             (const RepackJob*)repack_jobs, repack_njobs, (const float*)params, hb);
-          done = true;
-        } else if (mixed) {
-          hipLaunchKernelGGL((repack_all_kernel<float, true, true>), dim3(repack_blocks - hb), dim3(256), 0, s,
-                             (const RepackJob*)repack_jobs, repack_njobs, (const float*)params, hb);
-          done = true;
-        } else if (h2) {
-          hipLaunchKernelGGL((repack_all_kernel<float, true>), dim3(repack_blocks - hb), dim3(256), 0, s,
-                             (const RepackJob*)repack_jobs, repack_njobs, (const float*)params, hb);
-          done = true;
-        }
-      }
-      if (!done)
-        hipLaunchKernelGGL((repack_all_kernel<T>), dim3(repack_blocks - hb), dim3(256), 0, s,
-                           (const RepackJob*)repack_jobs, repack_njobs, (const float*)params, hb);
-    }
+    if (repack_blocks > hb) launch_repack(hb, repack_blocks - hb, repack_njobs, s);
     weights_dirty = false;
+  }
+  // workgroups [first_block, first_block + n_blocks) of the job table's first n_jobs jobs; the kernel by the two copies' formats
+  void launch_repack(int first_block, int n_blocks, int n_jobs, hipStream_t s) {
+    void (*kernel)(const RepackJob*, int, const float*, int) = repack_all_kernel<T>;
+    if constexpr (DT == MN_F32) {
+      if (md.wf == FMT_H2Q)  // forward operand h2q, data-gradient operand plain fp16
+        kernel = repack_all_kernel<float, true, true, true>;
+      else if (md.wf == FMT_H2 && md.wd == FMT_F16)  // forward operand h2, data-gradient operand plain fp16
+        kernel = repack_all_kernel<float, true, true>;
+      else if (md.wf == FMT_H2)
+        kernel = repack_all_kernel<float, true>;
+    }
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, (const RepackJob*)repack_jobs, n_jobs, (const float*)params,
+                       first_block);
   }
 
   // ---- forward ------------------------------------------------------------------------------------
@@ -745,30 +762,55 @@ struct Plan : PlanBase {
     p.momentum = 0.1f;
     return p;
   }
-  void conv_bn_stats(Unit& u, const T* x, int training, hipStream_t s) {
+  // no statistics, no bias, no ReLU, no residual, no gates, alpha 1: what every launch below starts from
+  static Epilogue plain_epilogue(void* out, int ldc) {
     Epilogue ep;
-    ep.out = u.y; ep.ldc = u.cp.cout; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0;
-    ep.res = nullptr; ep.res_gate = nullptr; ep.alpha = 1.f;
+    ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr; ep.res_gate = nullptr;
+    ep.alpha = 1.f;
+    return ep;
+  }
+  // a dense layer C[M][N] = A[M][K] * W[N][K]^T as a 1x1 convolution over M one-pixel images
+  static GatherGeom dense_geom(int M, int N, int K) {
+    GatherGeom g;
+    g.B = M; g.Hi = 1; g.Wi = 1; g.C = K; g.P = 1; g.Q = 1; g.R = 1; g.S = 1; g.mul_p = 1; g.mul_q = 1; g.rsign = 1;
+    g.ssign = 1; g.off_h = 0; g.off_w = 0; g.div = 1; g.M = M; g.N = N; g.K = K;
+    return g;
+  }
+  Epilogue stats_epilogue(Unit& u, int training) {  // raw conv output + (training) its column sums for the BatchNorm
+    Epilogue ep = plain_epilogue(u.y, u.cp.cout);
     if (training) {
       ep.stats_accum = u.accum_f;
       ep.stats_rows = u.rows_f;
     }
+    return ep;
+  }
+  // the convolution of a block unit (the stem has its own: stem_conv)
+  void conv_bn_stats(Unit& u, const T* x, int training, hipStream_t s) {
+    const Epilogue ep = stats_epilogue(u, training);
     auto* tp = timer.begin(0, s);
-    if (h2 && &u != &stem)  // h2 activation and weights in, fp32 conv output + statistics out
-      launch_igemm_h2(u.gf, (const half*)x, (const half*)u.wf, ep, s, (const half*)zero_page, q8);
-    else if (&u == &stem && DT == MN_F32 && mma_fwd == MMA_F16X3)  // the split-operand form of the stem kernel
-      launch_stem_conv_x3((const float*)x, (const float*)u.wf, (float*)u.y, training ? u.accum_f : nullptr, u.rows_f, B, H, W, Wp, s);
-    else if (&u == &stem && DT == MN_F16)  // weights in registers, input pairs read straight from LDS (stem.h)
-      launch_stem_conv((const half*)x, (const half*)u.wf, (half*)u.y, training ? u.accum_f : nullptr, u.rows_f, B, H, W, Wp, s);
+    if (md.pairs())  // h2 activation and weights in, fp32 conv output + statistics out
+      launch_igemm_h2(u.gf, (const half*)x, (const half*)u.wf, ep, s, (const half*)zero_page, md.act == FMT_H2Q);
     else if (halo_path(u.gf) && conv_halo_pp_applies(u.gf, ep))
       launch_conv_halo_pp(u.gf, (const half*)x, (const half*)u.wf, ep, s);
     else
       launch_igemm<T>(u.gf, x, u.wf, ep, s, (const T*)zero_page);
     timer.end(tp, s);
   }
+  // the stem reads 3 channels (no 32-channel groups, no halo): its own kernels, or the generic implicit GEMM on exact fp32
+  void stem_conv(int training, hipStream_t s) {
+    double* const sums = training ? stem.accum_f : nullptr;
+    auto* tp = timer.begin(0, s);
+    if (DT == MN_F32 && md.mma_fwd == MMA_F16X3)  // the split-operand form of the stem kernel
+      launch_stem_conv_x3((const float*)xpad, (const float*)stem.wf, (float*)stem.y, sums, stem.rows_f, B, H, W, Wp, s);
+    else if (DT == MN_F16)  // weights in registers, input pairs read straight from LDS (stem.h)
+      launch_stem_conv((const half*)xpad, (const half*)stem.wf, (half*)stem.y, sums, stem.rows_f, B, H, W, Wp, s);
+    else
+      launch_igemm<T>(stem.gf, xpad, stem.wf, stats_epilogue(stem, training), s, (const T*)zero_page);
+    timer.end(tp, s);
+  }
   // layer1's 64-channel 3x3 convolutions (forward and data gradient) run from an LDS-resident input halo in the
   // persistent two-group kernel of halo_pp.h; the shapes it does not cover go to the implicit-GEMM kernel
-  bool halo_path(const GatherGeom& g) const { return DT == MN_F16 && conv_halo_applies(g); }
+  bool halo_path(const GatherGeom& g) const { return md.act == FMT_F16 && conv_halo_applies(g); }
   void bn_finalize(Unit& u, hipStream_t s) {  // statistics -> (scale, shift), mean / invstd, running statistics
 #ifdef MN_ABLATION_BUILD
     const int skip_c = knobs().abl_skip_finalize;  // (see launch_bn_bwd)
@@ -781,10 +823,10 @@ struct Plan : PlanBase {
   void bn_act(Unit& u, const T* res, int relu, T* out, hipStream_t s) {
     long np = u.M * u.cp.cout / VEC;
     bn_finalize(u, s);
-    if (h2) {  // fp32 conv output in, h2 activation out (residual: an h2 activation)
+    if (md.pairs()) {  // fp32 conv output in, h2 activation out (residual: an h2 activation)
       const long ni = u.M * u.cp.cout / 8;
       hipLaunchKernelGGL(bn_apply_h2_kernel, dim3(ew_grid(ni)), dim3(256), 0, s, (const float*)u.y, (const float*)u.coef_f,
-                         (const half*)res, (half*)out, ni, u.cp.cout, relu, q8 ? 1 : 0,
+                         (const half*)res, (half*)out, ni, u.cp.cout, relu, md.act == FMT_H2Q ? 1 : 0,
                          cur_training ? u.rec : (half*)nullptr, (const float*)u.mean, (const float*)u.invstd);
       return;
     }
@@ -821,7 +863,7 @@ struct Plan : PlanBase {
       sqnorm_clean = true;
     }
     // (fp16x2m: the stem's fp16 backward kernels read an fp16 image of the input -- written by the same launch)
-    half* const x16 = stem_bwd_f16() && training ? xpad16 : (half*)nullptr;
+    half* const x16 = md.stem_bwd == STEM_TILES_ON_COPIES && training ? xpad16 : (half*)nullptr;
     if (resize_on) {  // Resize first: the conversion below reads the resized frames
       launch_resize_u8((const unsigned char*)images, rs_frames, rs_geom, s);
       images = rs_frames;
@@ -841,12 +883,12 @@ struct Plan : PlanBase {
       if (dirty) repack_tail(side);
       if (zero_grads) launch_zero_fill(grads, L.param_floats, side);
     }
-    conv_bn_stats(stem, xpad, training, s);
-    if (h2) {  // (always the fused form: fp32 conv output in, h2 pooled activation out)
+    stem_conv(training, s);
+    if (md.pairs()) {  // (always the fused form: fp32 conv output in, h2 pooled activation out)
       bn_finalize(stem, s);
       hipLaunchKernelGGL(bn_relu_maxpool_h2_kernel, dim3(ew_grid((long)B * H1 * W1 * 64 / 8)), dim3(256), 0, s,
                          (const float*)stem.y, (const float*)stem.coef_f, (half*)p0, pool_idx, B, H0, W0, 64, H1, W1,
-                         training && stem_bwd_f16() ? (half*)a0 : (half*)nullptr, q8 ? 1 : 0);
+                         training && md.stem_bwd == STEM_TILES_ON_COPIES ? (half*)a0 : (half*)nullptr, md.act == FMT_H2Q ? 1 : 0);
     } else if (fuse_stem) {  // BatchNorm + ReLU + max-pool in one pass; the normalised stem activation is never stored
       bn_finalize(stem, s);
       hipLaunchKernelGGL((bn_relu_maxpool_kernel<T>), dim3(ew_grid((long)B * H1 * W1 * 64 / VEC)), dim3(256), 0, s,
@@ -879,27 +921,24 @@ struct Plan : PlanBase {
     join_wgrad(s);
     const Block& last = blocks.back();
     int F = cfg.feat_dim;
-    if (h2)
+    if (md.pairs())
       hipLaunchKernelGGL(avgpool_fwd_h2_kernel, dim3(cdiv((long)B * 512, 256)), dim3(256), 0, s, (const half*)last.out, pooled,
-                         B, Hl * Wl, 512, q8 ? 1 : 0);
+                         B, Hl * Wl, 512, md.act == FMT_H2Q ? 1 : 0);
     else
       hipLaunchKernelGGL((avgpool_fwd_kernel<T>), dim3(cdiv((long)B * 512, 256)), dim3(256), 0, s, (const T*)last.out, pooled,
                          B, Hl * Wl, 512);
     // fc 512 -> feat_dim, bias, ReLU (models/posenet.py:46,65-66); dropout is the identity under the
     // reference's pinned torch 0.4.1 (F.dropout default training=False)
-    GatherGeom g;
-    g.B = B; g.Hi = 1; g.Wi = 1; g.C = 512; g.P = 1; g.Q = 1; g.R = 1; g.S = 1; g.mul_p = 1; g.mul_q = 1; g.rsign = 1;
-    g.ssign = 1; g.off_h = 0; g.off_w = 0; g.div = 1; g.M = B; g.N = F; g.K = 512;
-    Epilogue ep;
-    ep.out = feat; ep.ldc = F; ep.stats = nullptr; ep.bias = params + L.fc_b; ep.relu = 1; ep.res = nullptr;
-    ep.res_gate = nullptr; ep.alpha = 1.f;
+    Epilogue ep = plain_epilogue(feat, F);
+    ep.bias = params + L.fc_b;
+    ep.relu = 1;
     DenseArgs da;
     da.A = pooled; da.W = params + L.fc_w; da.bias = params + L.fc_b; da.C = feat; da.M = B; da.N = F; da.K = 512; da.lda = 512;
     da.ldw = 512; da.ldc = F; da.relu = 1;
     if (dense_nt_applies(da))  // 32 x 32 tiles, K split over the workgroup's waves (dense.h)
       launch_dense_nt(da, s);
     else
-      launch_igemm<float>(g, (const float*)pooled, (const float*)(params + L.fc_w), ep, s, (const float*)zero_page);
+      launch_igemm<float>(dense_geom(B, F, 512), (const float*)pooled, (const float*)(params + L.fc_w), ep, s, (const float*)zero_page);
     // F.dropout(x, p=droprate) (models/posenet.py:68-69), in training mode only (mn_set_dropout explains the reference's two
     // readings): a fresh Philox mask per training forward pass, kept for the backward pass
     drop_this_step = training && drop_p > 0.f;
@@ -938,96 +977,78 @@ struct Plan : PlanBase {
   }
 
   // ---- backward -------------------------------------------------------------------------------------
-  // self_gate: `gate` is relu(bn_u(y)) itself (a1 of a block, a0 of the stem): recomputed from y, not read
-  void bn_bwd(Unit& u, const T* g, const T* gate, hipStream_t s, bool self_gate = false) {
-    if (h2 && &u != &stem && gate && !self_gate) {
-      // (the h2 / fp16x2m apply kernels have no gate input -- block-output gradients arrive already gated -- so a
-      //  caller that passes a real gate must not get ungated gradients silently)
-      stage_error = "bn_bwd: the fp16x2 / fp16x2m modes take block-output gradients as stored (already gated); only self_gate exists";
-      return;  // (reported by backward_stage: this call site has no status to return)
-    }
-    if (mixed && &u != &stem && u.rec) {  // fp16 gradient and the forward pass's record in; plain fp16 d(conv output) out
-      launch_bn_bwd_rec((const half*)g, (const half*)u.rec, u.M, u.cp.cout, params + u.bp.gamma, u.mean, u.invstd, grads + u.bp.gamma,
+  // BatchNorm backward of a block unit.  `g` arrives already gated (block_backward) unless self_gate: then it is the gradient
+  // w.r.t. relu(bn_u(y)) -- a1 of the block -- and the gate is recomputed from y (or read from the record), never read from a1.
+  // No other gate exists, so none can be passed: the h2 / fp16x2m apply kernels have no gate input
+  void bn_bwd(Unit& u, const T* g, hipStream_t s, bool self_gate = false) {
+    float* const gamma = params + u.bp.gamma;
+    const float* const sg_beta = self_gate ? params + u.bp.beta : nullptr;
+    if (md.f16_bwd_on_pairs())  // fp16 gradient and the forward pass's record in; plain fp16 d(conv output) out
+      launch_bn_bwd_rec((const half*)g, (const half*)u.rec, u.M, u.cp.cout, gamma, u.mean, u.invstd, grads + u.bp.gamma,
                         grads + u.bp.beta, (half*)u.gy, u.accum_b, u.coef_b, 1.f / cur_scale, s, self_gate, u.rows_b);
-      return;
-    }
-    if (mixed && &u != &stem) {  // (MN_BN_REC=0) fp16 gradient, fp32 conv output in; plain fp16 d(conv output) out
-      launch_bn_bwd<half, float>((const half*)g, (const half*)nullptr, (const float*)u.y, u.M, u.cp.cout, params + u.bp.gamma, u.mean,
-                                 u.invstd, grads + u.bp.gamma, grads + u.bp.beta, (half*)u.gy, u.accum_b, u.coef_b, 1.f / cur_scale, s,
-                                 self_gate ? params + u.bp.beta : nullptr, PoolGradSrc(), u.rows_b);
-      return;
-    }
-    if (h2 && &u != &stem) {  // fp32 gradient and conv output in, h2 d(conv output) out; gates: none, or the unit's own ReLU
-      launch_bn_bwd_h2((const float*)g, (const float*)u.y, u.M, u.cp.cout, params + u.bp.gamma, u.mean, u.invstd,
-                       grads + u.bp.gamma, grads + u.bp.beta, (half*)u.gy, u.accum_b, u.coef_b, 1.f / cur_scale, s,
-                       self_gate ? params + u.bp.beta : nullptr, u.rows_b);
-      return;
-    }
-    launch_bn_bwd<T>(g, gate, (const T*)u.y, u.M, u.cp.cout, params + u.bp.gamma, u.mean, u.invstd, grads + u.bp.gamma,
-                     grads + u.bp.beta, u.gy, u.accum_b, u.coef_b, 1.f / cur_scale, s,
-                     self_gate ? params + u.bp.beta : nullptr, PoolGradSrc(), u.rows_b);
+    else if (md.gy == FMT_H2)  // fp32 gradient and conv output in, h2 d(conv output) out
+      launch_bn_bwd_h2((const float*)g, (const float*)u.y, u.M, u.cp.cout, gamma, u.mean, u.invstd, grads + u.bp.gamma,
+                       grads + u.bp.beta, (half*)u.gy, u.accum_b, u.coef_b, 1.f / cur_scale, s, sg_beta, u.rows_b);
+    else
+      launch_bn_bwd<T>(g, (const T*)nullptr, (const T*)u.y, u.M, u.cp.cout, gamma, u.mean, u.invstd, grads + u.bp.gamma,
+                       grads + u.bp.beta, u.gy, u.accum_b, u.coef_b, 1.f / cur_scale, s, sg_beta, PoolGradSrc(), u.rows_b);
   }
-  // bit 0: BatchNorm+ReLU+max-pool in one forward pass (-0.15 ms/step); bit 1: max-pool gradient gathered inside the
-  // BatchNorm backward passes instead of a maxpool_bwd launch (measured +0.05 ms/step: the gather runs twice) -- off
-  int fuse_stem_mask = knobs().fuse_stem;
-  bool fuse_stem = (fuse_stem_mask & 1) != 0;
-  bool fuse_stem_bwd = (fuse_stem_mask & 2) != 0;
-  bool early_fork = knobs().early_fork;
-  static constexpr bool parity_dgrad = true;  // stride-2 data gradients by parity class (dgrad.h: -1.6 % step time)
-  // `ws`: the stream the launch goes to (the side stream after a fork, or the main stream)
-  void conv_wgrad(Unit& u, const T* x, hipStream_t ws) {
+  WgradArgs wgrad_args(Unit& u, const T* x) {
     WgradArgs a;
     a.g = u.gf; a.dY = u.gy; a.ldy = u.cp.cout; a.X = x; a.dW = grads + u.cp.w; a.ldw = u.ldw; a.colmap = u.colmap;
-    a.g.mma = mma_bwd;
+    a.g.mma = md.mma_bwd;
     a.alpha = 1.f / cur_scale; a.rows_per_split = 0;
     a.ws = wgf_ws; a.ws_floats = wgf_ws_floats;  // every weight-gradient launch of a step goes to the same stream (`ws`)
     a.det = deterministic;
+    return a;
+  }
+  // reduction splits (measured, tools/conv_bench.py): one round of 2 workgroups per CU for the wide layers (half
+  // the atomic traffic of 1024), more for layer1 and the stem whose pixel dimension is 4-16x longer
+  static int wgrad_splits(const Unit& u) { return u.cp.cout >= 128 ? 512 : (u.M > 2000000 ? 2048 : 1024); }
+  // weight gradient of a block unit; `ws`: the stream the launch goes to (the side stream after a fork, or the main stream)
+  void conv_wgrad(Unit& u, const T* x, hipStream_t ws) {
+    WgradArgs a = wgrad_args(u, x);
     auto* tp = timer.begin(1, ws);
-    // reduction splits (measured, tools/conv_bench.py): one round of 2 workgroups per CU for the wide layers (half
-    // the atomic traffic of 1024), more for layer1 and the stem whose pixel dimension is 4-16x longer
-    const int target = u.cp.cout >= 128 ? 512 : (u.M > 2000000 ? 2048 : 1024);
-    if (mixed && &u != &stem) {  // plain fp16 d(conv output) against the HI halves of the h2 activation: the fp16 mode's kernels
+    if (md.f16_bwd_on_pairs()) {  // plain fp16 d(conv output) against the HI halves of the h2 activation: the fp16 mode's kernels
       a.g.mma = MMA_NATIVE;
       a.x_h2 = true;
-      launch_wgrad<half>(a, target, ws, zero_page);
-    } else if (h2 && &u != &stem) {  // h2 d(conv output) and activation
+      launch_wgrad<half>(a, wgrad_splits(u), ws, zero_page);
+    } else if (md.gy == FMT_H2) {  // h2 d(conv output) and activation
       a.g.mma = MMA_H2;
-      launch_wgrad<half>(a, target, ws, zero_page);
-    } else
-    launch_wgrad<T>(a, target, ws, zero_page);
+      launch_wgrad<half>(a, wgrad_splits(u), ws, zero_page);
+    } else {
+      launch_wgrad<T>(a, wgrad_splits(u), ws, zero_page);
+    }
     timer.end(tp, ws);
   }
-  void conv_dgrad(Unit& u, T* gx, const T* res, const T* gate, hipStream_t s, const T* out_gate = nullptr) {
-    Epilogue ep;
-    ep.out = gx; ep.ldc = u.cp.cin; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = res; ep.res_gate = gate;
+  // gx = data gradient of u (+ res), zeroed where out_gate <= 0
+  void conv_dgrad(Unit& u, T* gx, const T* res, hipStream_t s, const T* out_gate = nullptr) {
+    Epilogue ep = plain_epilogue(gx, u.cp.cin);
+    ep.res = res;
     ep.out_gate = out_gate;
-    ep.alpha = 1.f;
     auto* tp = timer.begin(0, s);
-    if (mixed) {  // the fp16 mode's launches: fp16 d(conv output), weights, gradient and residual; the gate = hi halves of the h2 activation
-      ep.gate_h2 = true;
+    if (md.gy == FMT_H2) {  // h2 d(conv output) and weights in, fp32 gradient out (+ fp32 residual, h2 gate of the block below)
+      launch_conv_dgrad<half>(u.dg, (const half*)u.gy, (const half*)u.wd, ep, s, (const half*)zero_page, parity_dgrad, true);
+    } else if (md.gy == FMT_F16) {  // the fp16 mode's launches: fp16 d(conv output), weights, gradient and residual
+      ep.gate_h2 = md.pairs();      // (fp16x2m: the gate = hi halves of the h2 activation)
       if (conv_halo_applies(u.dg.full) && conv_halo_pp_applies(u.dg.full, ep))
         launch_conv_halo_pp(u.dg.full, (const half*)u.gy, (const half*)u.wd, ep, s);
       else
         launch_conv_dgrad<half>(u.dg, (const half*)u.gy, (const half*)u.wd, ep, s, (const half*)zero_page, parity_dgrad);
-    } else if (h2)  // h2 d(conv output) and weights in, fp32 gradient out (+ fp32 residual, h2 gate of the block below)
-      launch_conv_dgrad<half>(u.dg, (const half*)u.gy, (const half*)u.wd, ep, s, (const half*)zero_page, parity_dgrad, true);
-    else if (halo_path(u.dg.full) && conv_halo_pp_applies(u.dg.full, ep))
-      launch_conv_halo_pp(u.dg.full, (const half*)u.gy, (const half*)u.wd, ep, s);
-    else
+    } else {
       launch_conv_dgrad<T>(u.dg, (const T*)u.gy, (const T*)u.wd, ep, s, (const T*)zero_page, parity_dgrad);
+    }
     timer.end(tp, s);
   }
-  // Weight-gradient schedule: the knobs, the per-mode defaults and their measurements are in knobs.h (resolve_wgrad_schedule);
-  // set in the constructor, once the mode is known
-  int wgrad_sched = 0;
-  int wgrad_tail = knobs().wgrad_tail;
-  int wgrad_early_stages = 15;
-  int wgrad_defer_stages = 0;
-  struct PendingWgrad {
-    Unit* u;
-    const T* x;
-  };
-  std::vector<PendingWgrad> pending_wgrads;
+  // the tail of a block's data gradient: gx = dgrad(u1) + the shortcut's gradient, gated by the ReLU `below` the block
+  void block_input_dgrad(Block& blk, const T* below, hipStream_t s) {
+    if (blk.down) {
+      conv_dgrad(blk.u1, blk.gx, nullptr, s, below);  // gated here too: the projection launch below may only touch the even pixels
+      conv_dgrad(blk.ud, blk.gx, blk.gx, s, below);   // accumulate the projection path in place, then gate
+    } else {
+      conv_dgrad(blk.u1, blk.gx, blk.gout, s, below);  // + identity path (already gated)
+    }
+  }
   void flush_wgrads(hipStream_t s) {
     if (pending_wgrads.empty()) return;
     hipStream_t ws = fork_wgrad(s);
@@ -1045,54 +1066,41 @@ struct Plan : PlanBase {
     const T* bx = blk.x;
     const T* ba1 = blk.a1;
     // (fp16x2m with the fp16 stem kernels: the gradient of the pooled stem activation leaves layer1.0 gated by that activation)
-    const T* below = &blk == &blocks.front() ? (stem_bwd_f16() ? bx : nullptr) : bx;
-    const T* og = nullptr;  // (bn2 / the projection / the identity path take `gout` as stored: already gated)
-    if (wgrad_sched == 2 || ((wgrad_defer_stages >> blk.stage) & 1)) {
+    const T* below = &blk == &blocks.front() ? (md.stem_bwd == STEM_TILES_ON_COPIES ? bx : nullptr) : bx;
+    // (bn2 / the projection / the identity path take `gout` as stored: already gated)
+    if (wgrad.sched == 2 || ((wgrad.defer_stages >> blk.stage) & 1)) {
       flush_wgrads(s);
-      bn_bwd(blk.u2, blk.gout, og, s);
-      if (!stage_error.empty()) return;
-      conv_dgrad(blk.u2, blk.ga1, nullptr, nullptr, s);
+      bn_bwd(blk.u2, blk.gout, s);
+      conv_dgrad(blk.u2, blk.ga1, nullptr, s);
       pending_wgrads.push_back({&blk.u2, ba1});
       flush_wgrads(s);
-      bn_bwd(blk.u1, blk.ga1, ba1, s, true);
-      if (blk.down) bn_bwd(blk.ud, blk.gout, og, s);
+      bn_bwd(blk.u1, blk.ga1, s, true);
+      if (blk.down) bn_bwd(blk.ud, blk.gout, s);
       pending_wgrads.push_back({&blk.u1, bx});
-      if (blk.down) {
-        pending_wgrads.push_back({&blk.ud, bx});
-        conv_dgrad(blk.u1, blk.gx, nullptr, nullptr, s, below);  // gated here too: the projection launch below may only touch the even pixels
-        conv_dgrad(blk.ud, blk.gx, blk.gx, nullptr, s, below);
-      } else {
-        conv_dgrad(blk.u1, blk.gx, blk.gout, og, s, below);
-      }
+      if (blk.down) pending_wgrads.push_back({&blk.ud, bx});
+      block_input_dgrad(blk, below, s);
       return;
     }
-    bn_bwd(blk.u2, blk.gout, og, s);
-    if (!stage_error.empty()) return;  // (round-5 ADVICE: do not run data / weight gradients on a d(conv output) that was never written)
+    bn_bwd(blk.u2, blk.gout, s);
     // MN_WGRAD_TAIL = k: the weight gradients of the first k blocks of layer1 (the LAST k of the backward pass) are held back and
     // forked in front of the stem's backward kernels (backward_stage: flush_wgrads), which run alone on the step stream at the end of
     // the step and are VALU-bound -- the matrix pipe is idle under them.  Same stage, same gradient bucket.
     const bool tail = blk.stage == 0 && !blk.down && (int)(&blk - &blocks[0]) < wgrad_tail;
-    const bool early = wgrad_sched == 1 && !tail && ((wgrad_early_stages >> blk.stage) & 1);
+    const bool early = wgrad.sched == 1 && !tail && ((wgrad.early_stages >> blk.stage) & 1);
     if (early) conv_wgrad(blk.u2, ba1, fork_wgrad(s));
-    conv_dgrad(blk.u2, blk.ga1, nullptr, nullptr, s);
-    bn_bwd(blk.u1, blk.ga1, ba1, s, true);
-    if (blk.down) bn_bwd(blk.ud, blk.gout, og, s);
+    conv_dgrad(blk.u2, blk.ga1, nullptr, s);
+    bn_bwd(blk.u1, blk.ga1, s, true);
+    if (blk.down) bn_bwd(blk.ud, blk.gout, s);
     if (tail) {
       pending_wgrads.push_back({&blk.u2, ba1});
       pending_wgrads.push_back({&blk.u1, bx});
-      conv_dgrad(blk.u1, blk.gx, blk.gout, og, s, below);
-      return;
-    }
-    hipStream_t ws = fork_wgrad(s);
-    if (!early) conv_wgrad(blk.u2, ba1, ws);
-    conv_wgrad(blk.u1, bx, ws);
-    if (blk.down) {
-      conv_wgrad(blk.ud, bx, ws);
-      conv_dgrad(blk.u1, blk.gx, nullptr, nullptr, s, below);  // gated here too: the projection launch below may only touch the even pixels
-      conv_dgrad(blk.ud, blk.gx, blk.gx, nullptr, s, below);  // accumulate the projection path in place, then gate
     } else {
-      conv_dgrad(blk.u1, blk.gx, blk.gout, og, s, below);  // + identity path (already gated)
+      hipStream_t ws = fork_wgrad(s);
+      if (!early) conv_wgrad(blk.u2, ba1, ws);
+      conv_wgrad(blk.u1, bx, ws);
+      if (blk.down) conv_wgrad(blk.ud, bx, ws);
     }
+    block_input_dgrad(blk, below, s);
   }
   void launch_head_wgrads(hipStream_t st) override {
     const int F = cfg.feat_dim;
@@ -1106,6 +1114,18 @@ struct Plan : PlanBase {
     dw.ldx = 512; dw.ldw = 512; dw.alpha = unscale;
     launch_dense_wgrad(dw, st);
     head_wgrads_deferred = false;
+  }
+  // dpooled = dz * fc_w: 32 x 32 tiles with K split over the workgroup's waves (dense.h) where that form applies
+  void fc_dgrad(hipStream_t s) {
+    const int F = cfg.feat_dim;
+    DenseArgs dd;
+    dd.A = dz; dd.W = fcT; dd.bias = nullptr; dd.C = dpooled; dd.M = B; dd.N = 512; dd.K = F; dd.lda = F; dd.ldw = F; dd.ldc = 512;
+    dd.relu = 0;
+    if (dense_nt_applies(dd))
+      launch_dense_nt(dd, s);
+    else
+      launch_igemm<float>(dense_geom(B, 512, F), (const float*)dz, (const float*)fcT, plain_epilogue(dpooled, 512), s,
+                          (const float*)zero_page);
   }
   void head_backward(hipStream_t s) {
     int F = cfg.feat_dim;
@@ -1124,83 +1144,67 @@ struct Plan : PlanBase {
       head_wgrads_deferred = true;
     else
       launch_head_wgrads(s);
-    GatherGeom g;
-    g.B = B; g.Hi = 1; g.Wi = 1; g.C = 512; g.P = 1; g.Q = 1; g.R = 1; g.S = 1; g.mul_p = 1; g.mul_q = 1; g.rsign = 1;
-    g.ssign = 1; g.off_h = 0; g.off_w = 0; g.div = 1; g.M = B; g.N = F; g.K = 512;
-    GatherGeom gd = g;
-    gd.C = F; gd.N = 512; gd.K = F;
-    Epilogue ep;
-    ep.out = dpooled; ep.ldc = 512; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr;
-    ep.res_gate = nullptr; ep.alpha = 1.f;
-    DenseArgs dd;
-    dd.A = dz; dd.W = fcT; dd.bias = nullptr; dd.C = dpooled; dd.M = B; dd.N = 512; dd.K = F; dd.lda = F; dd.ldw = F; dd.ldc = 512;
-    dd.relu = 0;
-    if (dense_nt_applies(dd))
-      launch_dense_nt(dd, s);
-    else
-      launch_igemm<float>(gd, (const float*)dz, (const float*)fcT, ep, s, (const float*)zero_page);
+    fc_dgrad(s);
     Block& last = blocks.back();
-    if (mixed)  // fp16 gradient out, gate = the hi halves of the last block's h2 output
+    if (md.f16_bwd_on_pairs())  // fp16 gradient out, gate = the hi halves of the last block's h2 output
       hipLaunchKernelGGL((avgpool_bwd_kernel<half>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s,
                          (const float*)dpooled, (half*)last.gout, B, Hl * Wl, 512, (const half*)last.out, 1);
-    else if (h2)
+    else if (md.pairs())
       hipLaunchKernelGGL(avgpool_bwd_h2_kernel, dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s, (const float*)dpooled,
                          (float*)last.gout, B, Hl * Wl, 512, (const half*)last.out);
     else
       hipLaunchKernelGGL((avgpool_bwd_kernel<T>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s,
                          (const float*)dpooled, last.gout, B, Hl * Wl, 512, (const T*)last.out, 0);
   }
-  // (MN_DETERMINISTIC: the stem's backward goes through bn_bwd + the split-slice weight gradient instead)
-  bool use_stem_bwd = DT == MN_F16 && !deterministic;
-  // fp16x2m: the same two kernels on fp16 COPIES of the fp32 conv output (written by the stem's BatchNorm + max-pool pass) and of
-  // the padded input, with the pooled gradient arriving already gated (StemBwdArgs::pre_gated); MN_DETERMINISTIC
-  // keeps the fp32 chain of fp16x2
-  bool stem_f16 = false;  // (set in the constructor, once `mixed` is known)
-  bool stem_bwd_f16() const { return stem_f16; }
   void stem_backward(hipStream_t s) {
-    if (use_stem_bwd || stem_bwd_f16()) {
-      const bool mx = stem_bwd_f16();
+    float* const gamma = params + stem.bp.gamma;
+    float* const beta = params + stem.bp.beta;
+    if (md.stem_bwd != STEM_CHAIN) {
+      const bool mx = md.stem_bwd == STEM_TILES_ON_COPIES;
       // two tile-walking launches (stem_bwd.h): BatchNorm sums, then the weight gradient with d(conv output) computed tile
       // by tile in LDS -- neither the max-pool's input gradient nor d(conv output) is stored
       StemBwdArgs a;
-      a.y = mx ? (const half*)a0 : (const half*)stem.y; a.idx = pool_idx; a.gp = (const half*)gp0; a.gamma = params + stem.bp.gamma;
-      a.beta = params + stem.bp.beta; a.coef = stem.coef_b; a.mean = stem.mean; a.invstd = stem.invstd; a.accum = stem.accum_b;
+      a.y = mx ? (const half*)a0 : (const half*)stem.y; a.idx = pool_idx; a.gp = (const half*)gp0; a.gamma = gamma;
+      a.beta = beta; a.coef = stem.coef_b; a.mean = stem.mean; a.invstd = stem.invstd; a.accum = stem.accum_b;
       a.accum_rows = stem.rows_b; a.xpad = mx ? (const half*)xpad16 : (const half*)xpad; a.dW = grads + stem.cp.w;
       a.colmap = stem_colmap; a.ldw = stem.ldw;
       a.alpha = 1.f / cur_scale;
       a.pre_gated = mx ? 1 : 0;
       launch_stem_bn_reduce(a, B, H, W, Wp, s);
       hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(64 / kBnFinalizeChannels), dim3(256), 0, s, (const double*)stem.accum_b, (double)stem.M,
-                         (const float*)(params + stem.bp.gamma), (const float*)stem.mean, (const float*)stem.invstd,
-                         grads + stem.bp.gamma, grads + stem.bp.beta, 1.f / cur_scale, (const float*)(params + stem.bp.beta),
-                         stem.coef_b, 64, stem.rows_b);
+                         (const float*)gamma, (const float*)stem.mean, (const float*)stem.invstd, grads + stem.bp.gamma,
+                         grads + stem.bp.beta, 1.f / cur_scale, (const float*)beta, stem.coef_b, 64, stem.rows_b);
       auto* tp = timer.begin(1, s);
       launch_stem_wgrad(a, B, H, W, Wp, s);
       timer.end(tp, s);
       return;
     }
-    if (fuse_stem_bwd || h2) {  // (fp16x2: the stem's fp32 tensors make the materialised 1 GB gradient cost 0.5 ms per step)
+    // the chain: BatchNorm backward with the stem's own ReLU gate recomputed from y, then the generic weight gradient
+    const T* g = nullptr;
+    PoolGradSrc pg;
+    if (fuse_stem_bwd || md.pairs()) {  // (fp16x2: the stem's fp32 tensors make the materialised 1 GB gradient cost 0.5 ms per step)
       // the max-pool's input gradient is gathered from (argmax, pooled gradient) inside the BatchNorm backward
-      // passes and the ReLU gate is recomputed from y: neither the activation nor its gradient exists in memory
-      PoolGradSrc pg;
+      // passes: neither the activation nor its gradient exists in memory
       pg.idx = pool_idx; pg.gout = gp0; pg.H = H0; pg.W = W0; pg.Po = H1; pg.Qo = W1;
-      if (mixed) {  // layer1.0's data gradient left gp0 in fp16: widened into ga0 (unused by the fused stem) for the fp32 chain
+      if (md.gx != md.y) {  // layer1.0's data gradient left gp0 in fp16: widened into ga0 (unused by the fused stem) for the fp32 chain
         const long n1 = (long)B * H1 * W1 * 64;
         hipLaunchKernelGGL(widen_f16_kernel, dim3(ew_grid(n1 / 8)), dim3(256), 0, s, (const half*)gp0, (float*)ga0, n1 / 8);
         pg.gout = ga0;
       }
-      launch_bn_bwd<T>((const T*)nullptr, (const T*)nullptr, (const T*)stem.y, stem.M, 64, params + stem.bp.gamma, stem.mean,
-                       stem.invstd, grads + stem.bp.gamma, grads + stem.bp.beta, stem.gy, stem.accum_b, stem.coef_b,
-                       1.f / cur_scale, s, params + stem.bp.beta, pg, stem.rows_b);
     } else {
       hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid((long)B * H0 * W0 * 64 / VEC)), dim3(256), 0, s,
                          (const unsigned char*)pool_idx, (const T*)gp0, ga0, B, H0, W0, 64, H1, W1);
-      bn_bwd(stem, ga0, a0, s, true);
+      g = ga0;
     }
+    launch_bn_bwd<T>(g, (const T*)nullptr, (const T*)stem.y, stem.M, 64, gamma, stem.mean, stem.invstd, grads + stem.bp.gamma,
+                     grads + stem.bp.beta, stem.gy, stem.accum_b, stem.coef_b, 1.f / cur_scale, s, beta, pg, stem.rows_b);
     // The input gradient of the stem is not needed (nothing consumes it).  The weight gradient goes to the stream every
     // other weight gradient of the step runs on: they share the partial-tile / split-slice workspace (wgf_ws), and the
     // last layer1 launches forked a moment ago may still be using it (joined at the end of the stage).
-    conv_wgrad(stem, xpad, fork_wgrad(s));
+    hipStream_t ws = fork_wgrad(s);
+    auto* tp = timer.begin(1, ws);
+    launch_wgrad<T>(wgrad_args(stem, xpad), wgrad_splits(stem), ws, zero_page);
+    timer.end(tp, ws);
   }
   // ---- input gradient at inference (mn_input_grad) ---------------------------------------------------------------------
   // d(sum(cot * poses)) / d(images) in eval mode: the eval forward pass, then the data-gradient chain alone, on the step stream.
@@ -1212,7 +1216,7 @@ struct Plan : PlanBase {
                           u.gy, u.M, u.cp.cout, s);
   }
   int input_grad(const void* images, const float* cot, float* gx_out, float* sal_out, float* poses_out, hipStream_t s) override {
-    if (h2)
+    if (md.pairs())
       return fail("mn_input_grad: supported dtypes are MN_DTYPE_F32, MN_DTYPE_F32X3 and MN_DTYPE_F16 (the fp16x2 / fp16x2m / fp16x2q "
                   "modes have no inference backward pass)");
     if (jitter_on())
@@ -1228,19 +1232,7 @@ struct Plan : PlanBase {
     hipLaunchKernelGGL(head_bwd_input_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, s, (const float*)dposes,
                        (const float*)feat, (const float*)(params + L.xyz_w), (const float*)(params + L.wpqr_w), dz, B, F,
                        cfg.filter_nans, (const float*)nullptr);
-    GatherGeom gd;
-    gd.B = B; gd.Hi = 1; gd.Wi = 1; gd.C = F; gd.P = 1; gd.Q = 1; gd.R = 1; gd.S = 1; gd.mul_p = 1; gd.mul_q = 1; gd.rsign = 1;
-    gd.ssign = 1; gd.off_h = 0; gd.off_w = 0; gd.div = 1; gd.M = B; gd.N = 512; gd.K = F;
-    Epilogue ep;
-    ep.out = dpooled; ep.ldc = 512; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr;
-    ep.res_gate = nullptr; ep.alpha = 1.f;
-    DenseArgs dd;
-    dd.A = dz; dd.W = fcT; dd.bias = nullptr; dd.C = dpooled; dd.M = B; dd.N = 512; dd.K = F; dd.lda = F; dd.ldw = F; dd.ldc = 512;
-    dd.relu = 0;
-    if (dense_nt_applies(dd))
-      launch_dense_nt(dd, s);
-    else
-      launch_igemm<float>(gd, (const float*)dz, (const float*)fcT, ep, s, (const float*)zero_page);
+    fc_dgrad(s);
     Block& last = blocks.back();
     hipLaunchKernelGGL((avgpool_bwd_kernel<T>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s, (const float*)dpooled,
                        last.gout, B, Hl * Wl, 512, (const T*)last.out, 0);
@@ -1248,15 +1240,10 @@ struct Plan : PlanBase {
       Block& blk = blocks[i];
       const T* below = i == 0 ? (const T*)nullptr : blk.x;  // (block_backward: the ReLU that produced this block's input)
       bn_eval_bwd(blk.u2, blk.gout, nullptr, false, s);
-      conv_dgrad(blk.u2, blk.ga1, nullptr, nullptr, s);
+      conv_dgrad(blk.u2, blk.ga1, nullptr, s);
       bn_eval_bwd(blk.u1, blk.ga1, blk.a1, false, s);
-      if (blk.down) {
-        bn_eval_bwd(blk.ud, blk.gout, nullptr, false, s);
-        conv_dgrad(blk.u1, blk.gx, nullptr, nullptr, s, below);
-        conv_dgrad(blk.ud, blk.gx, blk.gx, nullptr, s, below);
-      } else {
-        conv_dgrad(blk.u1, blk.gx, blk.gout, nullptr, s, below);
-      }
+      if (blk.down) bn_eval_bwd(blk.ud, blk.gout, nullptr, false, s);
+      block_input_dgrad(blk, below, s);
     }
     hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid((long)B * H0 * W0 * 64 / VEC)), dim3(256), 0, s,
                        (const unsigned char*)pool_idx, (const T*)gp0, ga0, B, H0, W0, 64, H1, W1);
@@ -1277,21 +1264,15 @@ struct Plan : PlanBase {
     if (stage < 0 || stage > 3) return fail("backward_stage: stage must be 0..3");
     if (!cur_targets) return fail("backward_stage: call mn_train_forward_loss first");
     if (stage == 3) head_backward(s);
-    // (a launch helper that refuses its arguments -- bn_bwd -- records stage_error: nothing that depends on its output is launched)
-    for (int i = (int)blocks.size() - 1; i >= 0 && stage_error.empty(); --i)
+    for (int i = (int)blocks.size() - 1; i >= 0; --i)
       if (blocks[i].stage == stage) block_backward(blocks[i], s);
-    if (stage == 0 && stage_error.empty()) {
+    if (stage == 0) {
       flush_wgrads(s);  // beside the stem's BatchNorm backward
       stem_backward(s);
     }
     flush_wgrads(s);
     if (head_wgrads_deferred) launch_head_wgrads(s);  // (no fork took them along)
     join_wgrad(s);  // the stage's gradient bucket is complete when this call's work on s is
-    if (!stage_error.empty()) {  // a launch helper refused its arguments (bn_bwd): the stage is incomplete
-      const std::string e = stage_error;
-      stage_error.clear();
-      return fail(e);
-    }
     return check_launch("backward_stage");
   }
 
@@ -1306,12 +1287,10 @@ struct Plan : PlanBase {
       return 0;
     };
     const long n0 = (long)B * H0 * W0 * 64, n1 = (long)B * H1 * W1 * 64;
+    const int AT = md.act, GT = md.gy, GD = md.gx;
     if (n == "xpad") return give(xpad, (long)B * Hp * Wp * 4, DT);
     if (n == "stem.y") return give(stem.y, n0, DT);
     if (n == "stem.gy") return give(stem.gy, n0, DT);
-    const int AT = q8 ? MN_DTYPE_F16X2Q : h2 ? MN_DTYPE_F16X2 : DT;  // dtype code of the tensors the convolutions consume (h2 / h2q)
-    // fp16x2m: d(conv output) and the data gradients are plain fp16 (in buffers carved for 4 bytes per element)
-    const int GT = mixed ? MN_F16 : AT, GD = mixed ? MN_F16 : DT;
     if (n == "p0") return give(p0, n1, AT);
     if (n == "gp0") return give(gp0, n1, GD);
     if (n == "pooled") return give(pooled, (long)B * 512, MN_F32);
@@ -1368,7 +1347,7 @@ struct Plan : PlanBase {
   }
   int optim_step(float grad_mul, hipStream_t s) override {
     // squared gradient norm: for clip_grad_norm, and (fp16) as the overflow detector of this step
-    if (max_grad_norm > 0.f || overflow_guard) {
+    if (max_grad_norm > 0.f || md.overflow_guard) {
       const int nb = sqnorm_grid(L.model_floats);
       if (deterministic && nb <= kSqPartials) {
         hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, s, (const float*)grads, (long)L.model_floats, sqnorm,
@@ -1383,20 +1362,26 @@ struct Plan : PlanBase {
     }
     attempts += 1;
     hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, step_dev, beta1, beta2, bc_dev, (const double*)sqnorm,
-                       overflow_guard ? overflow_dev : (long long*)nullptr, (long long)attempts);
+                       md.overflow_guard ? overflow_dev : (long long*)nullptr, (long long)attempts);
     AdamArgs a;
     a.p = params; a.g = grads; a.m = m1; a.v = m2; a.n = L.param_floats; a.n_clip = L.model_floats; a.lr = lr; a.wd = wd;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
     a.bc1 = 1.f; a.bc2 = 1.f; a.bc_dev = bc_dev;
     a.grad_mul = grad_mul; a.max_norm = max_grad_norm; a.sqnorm = sqnorm; a.frozen = frozen; a.eps_mode = cfg.eps_mode;
-    a.skip = overflow_guard ? overflow_dev : nullptr;
+    a.skip = md.overflow_guard ? overflow_dev : nullptr;
     a.method = optim_method; a.nesterov = nesterov;
     hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(L.param_floats)), dim3(256), 0, s, a);
-    if (overflow_guard && overflow_host)
+    if (md.overflow_guard && overflow_host)
       hipMemcpyAsync(overflow_host, overflow_dev, 4 * sizeof(long long), hipMemcpyDeviceToHost, s);
     return check_launch("optim_step");
   }
 };
+
+// the storage type T is the only thing chosen here: what else a dtype means is Plan::mode_of's
+std::unique_ptr<PlanBase> make_plan(const mn_config& cfg) {
+  if (cfg.dtype == MN_DTYPE_F16) return std::unique_ptr<PlanBase>(new Plan<half>(cfg));
+  return std::unique_ptr<PlanBase>(new Plan<float>(cfg));
+}
 
 }  // namespace
 
@@ -1428,12 +1413,7 @@ static int validate(const mn_config* c) {
 extern "C" int64_t mn_plan_bytes(const mn_config* cfg) {
   if (validate(cfg)) return -1;
   load_knobs();
-  if (cfg->dtype == MN_DTYPE_F16) {
-    Plan<half> p(*cfg);
-    return (int64_t)p.carve(nullptr);
-  }
-  Plan<float> p(*cfg);
-  return (int64_t)p.carve(nullptr);
+  return (int64_t)make_plan(*cfg)->carve(nullptr);
 }
 
 extern "C" mn_handle* mn_create(const mn_config* cfg, float* params, float* opt_state, void* buffers, void* work,
@@ -1446,17 +1426,8 @@ extern "C" mn_handle* mn_create(const mn_config* cfg, float* params, float* opt_
   mn_handle* h = new mn_handle();
   begin_call();
   load_knobs();
-  int rc;
-  if (cfg->dtype == MN_DTYPE_F16) {
-    auto* p = new Plan<half>(*cfg);
-    h->plan.reset(p);
-    rc = p->attach(params, opt_state, buffers, work, (hipStream_t)stream);
-  } else {
-    auto* p = new Plan<float>(*cfg);
-    h->plan.reset(p);
-    rc = p->attach(params, opt_state, buffers, work, (hipStream_t)stream);
-  }
-  if (rc) {
+  h->plan = make_plan(*cfg);
+  if (h->plan->attach(params, opt_state, buffers, work, (hipStream_t)stream)) {
     delete h;
     return nullptr;
   }
@@ -1473,10 +1444,7 @@ extern "C" int mn_set_learn_flags(mn_handle* h, int learn_beta, int learn_gamma)
   MN_H(h);
   P.learn_beta = learn_beta;
   P.learn_gamma = learn_gamma;
-  if (P.cfg.dtype == MN_DTYPE_F16)
-    static_cast<Plan<half>&>(P).update_frozen(nullptr);
-  else
-    static_cast<Plan<float>&>(P).update_frozen(nullptr);
+  P.update_frozen(nullptr);
   return 0;
 }
 extern "C" int mn_set_loss_fn(mn_handle* h, int t_kind, float t_param, int q_kind, float q_param) {
