@@ -63,6 +63,8 @@ _PROTOS = {
     "mn_set_color_jitter_calls": (c_i, [c_void, C.c_uint32]),
     "mn_input_resize_bytes": (c_i64, [C.POINTER(Config), c_i, c_i]),
     "mn_set_input_resize": (c_i, [c_void, c_i, c_i, c_void, c_i64]),
+    "mn_input_index_bytes": (c_i64, [C.POINTER(Config), c_i]),
+    "mn_set_input_index": (c_i, [c_void, c_void, c_i64, c_void, c_i64]),
     "mn_forward": (c_i, [c_void, c_void, c_void, c_i, c_void]),
     "mn_input_grad": (c_i, [c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "mn_loss": (c_i, [c_void, c_void, c_void, c_void, c_void]),
@@ -129,6 +131,8 @@ _PROTOS = {
     "mn_op_resize_u8": (c_i, [c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_i, c_void]),
     "mn_op_resize_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
     "mn_op_resize_tile": (c_i, [c_i, c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
+    "mn_op_gather_frames": (c_i, [c_void, c_void, c_void, c_i64, c_i, c_i64, c_void, c_void]),
+    "mn_op_resize_u8_indexed": (c_i, [c_void, c_void, c_i64, c_void, c_void, c_i, c_i, c_i, c_i, c_i, c_void, c_void]),
     "mn_op_stem_dgrad": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_f, c_void]),
     "mn_op_bn_eval_bwd": (c_i, [c_i, c_void, c_void, c_void, c_void, c_i64, c_i, c_void]),
     "mn_op_saliency": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, c_void]),

@@ -15,6 +15,7 @@
 #include "elementwise.h"
 #include "elementwise_h2.h"
 #include "head.h"
+#include "gather.h"
 #include "jitter.h"
 #include "resize.h"
 #include "knobs.h"
@@ -216,6 +217,13 @@ struct PlanBase {
   bool resize_on = false;
   ResizeGeom rs_geom;
   unsigned char* rs_frames = nullptr;
+  // Frames gathered from a device-resident store (mn_set_input_index): `images` is the store's base and image b of the batch is
+  // frame in_index[b] of it -- read by the indexed resample where the resize is on, else gathered into the caller's buffer in_stage
+  // at the head of a pass; everything downstream reads the gathered batch where it read `images`.  Off (null): nothing is launched
+  const int32_t* in_index = nullptr;
+  int64_t in_store_frames = 0;
+  unsigned char* in_stage = nullptr;
+  int64_t in_stage_bytes = 0;
   virtual int input_grad(const void* images, const float* cot, float* gx_out, float* sal_out, float* poses_out, hipStream_t s) = 0;
   virtual int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) = 0;
   virtual int forward_loss(const void* images, const float* targets, float* loss_out, float* poses_out,
@@ -434,6 +442,8 @@ struct Plan : PlanBase {
   float *pooled, *feat, *poses, *dposes, *dz, *dpooled, *fcT, *loss_dev, *dropmask;
   float *jit_draws, *jit_partials, *jit_mean;  // ColorJitter: [B][8] draws, [B][kJitterChunks] gray sums, [B] mean gray
   float *ig_flag, *sal_work;  // input_grad: {1 if the last call's gradient held a non-finite value}, [B][kSalChunks][2] (min, max)
+  // mn_set_input_index: 1 if an index of the last indexed pass lay outside the store -- the second float of ig_flag's 256 bytes
+  float* index_flag() const { return ig_flag + 1; }
   // BatchNorm sums are accumulated with fp64 atomics straight from the producing kernels (conv epilogue, backward
   // reduction) into ACC_ROWS rows per unit (row = producer block % ACC_ROWS, to spread same-address contention);
   // the consuming apply kernels add the rows in their prologue.  No separate partial-reduction launches.
@@ -851,7 +861,11 @@ struct Plan : PlanBase {
     if (resize_on && !input_u8)
       return fail("forward: Resize (mn_set_input_resize) needs uint8 input (mn_set_input_u8): fp32 frames arrive already "
                   "normalised, and Resize must come before Normalize");
-    if (resize_on && !images) return fail("forward: images are required");
+    if ((resize_on || in_index) && !images) return fail("forward: images are required");
+    const int64_t batch_bytes = (int64_t)B * H * W * 3 * (input_u8 ? 1 : 4);
+    if (in_index && !resize_on && (!in_stage || in_stage_bytes < batch_bytes))
+      return fail("forward: the staging buffer of mn_set_input_index holds " + std::to_string((long long)in_stage_bytes) +
+                  " bytes, the gathered batch needs " + std::to_string((long long)batch_bytes) + " (mn_input_index_bytes)");
     // work the stem and layer1 do not depend on goes to the side stream: the repack of the later layers'
     // weights and optim.learner.zero_grad(); joined before layer2
     const bool dirty = weights_dirty;
@@ -864,8 +878,15 @@ struct Plan : PlanBase {
     }
     // (fp16x2m: the stem's fp16 backward kernels read an fp16 image of the input -- written by the same launch)
     half* const x16 = md.stem_bwd == STEM_TILES_ON_COPIES && training ? xpad16 : (half*)nullptr;
+    if (in_index) {  // frames come from a store: the flag of an index outside it starts every pass at 0
+      hipMemsetAsync(index_flag(), 0, sizeof(float), s);
+      if (!resize_on) {
+        launch_gather_frames(images, in_index, in_stage, batch_bytes / B, B, in_store_frames, index_flag(), s);
+        images = in_stage;
+      }
+    }
     if (resize_on) {  // Resize first: the conversion below reads the resized frames
-      launch_resize_u8((const unsigned char*)images, rs_frames, rs_geom, s);
+      launch_resize_u8((const unsigned char*)images, rs_frames, rs_geom, s, in_index, in_store_frames, index_flag());
       images = rs_frames;
     }
     if (input_u8 && jitter_on())
@@ -1225,6 +1246,7 @@ struct Plan : PlanBase {
     if (!images || !gx_out) return fail("mn_input_grad: images and gx_out are required");
     if (int e = forward_impl(images, poses_out, 0, false, s)) return e;
     if (resize_on) images = rs_frames;  // the x of the saliency map: the frames the network saw
+    else if (in_index) images = in_stage;
     const int F = cfg.feat_dim;
     hipMemsetAsync(ig_flag, 0, sizeof(float), s);
     hipLaunchKernelGGL(input_grad_seed_kernel, dim3(cdiv((long)B * 6, 256)), dim3(256), 0, s, cot, dposes, B * 6, 1.f / (6.f * (float)B),
@@ -1302,6 +1324,7 @@ struct Plan : PlanBase {
     if (n == "dropmask") return give(dropmask, (long)B * cfg.feat_dim, MN_F32);
     if (n == "jitter") return give(jit_draws, (long)B * 8, MN_F32);
     if (n == "input_grad_nonfinite") return give(ig_flag, 1, MN_F32);
+    if (n == "input_index_bad") return give(index_flag(), 1, MN_F32);
     if (n.size() > 2 && n[0] == 'b') {  // "b<block>.<tensor>", blocks numbered 0..15 in network order
       const size_t dot = n.find('.');
       if (dot != std::string::npos) {
@@ -1599,6 +1622,35 @@ extern "C" int mn_set_input_resize(mn_handle* h, int src_h, int src_w, void* wor
   P.rs_geom = rp.g;
   P.rs_frames = (unsigned char*)work;
   P.resize_on = true;
+  return 0;
+}
+extern "C" int64_t mn_input_index_bytes(const mn_config* cfg, int input_u8) {
+  if (validate(cfg)) return -1;
+  return (int64_t)resize_images(cfg) * 3 * cfg->H * cfg->W * (input_u8 ? 1 : 4);
+}
+extern "C" int mn_set_input_index(mn_handle* h, const int32_t* index_dev, int64_t store_frames, void* work, int64_t work_bytes) {
+  MN_H(h);
+  if (!index_dev) {
+    P.in_index = nullptr;
+    P.in_store_frames = 0;
+    P.in_stage = nullptr;
+    P.in_stage_bytes = 0;
+    return 0;
+  }
+  if (((uintptr_t)index_dev & 3) != 0) return fail("mn_set_input_index: index_dev must be 4-byte aligned (device int32 [images])");
+  if (store_frames < 1) return fail("mn_set_input_index: store_frames must be at least 1");
+  if (resize_images(&P.cfg) > 65535) return fail("mn_set_input_index: at most 65535 frames per pass (the gather's grid)");
+  if (!P.resize_on) {  // (with the resize on the resample reads the store itself: no staging)
+    const int64_t need = mn_input_index_bytes(&P.cfg, P.input_u8 ? 1 : 0);
+    if (!work) return fail("mn_set_input_index: work (device memory of mn_input_index_bytes) is required");
+    if (work_bytes < need)
+      return fail("mn_set_input_index: work holds " + std::to_string((long long)work_bytes) + " bytes, mn_input_index_bytes asks for " +
+                  std::to_string((long long)need));
+  }
+  P.in_index = index_dev;
+  P.in_store_frames = store_frames;
+  P.in_stage = P.resize_on ? nullptr : (unsigned char*)work;
+  P.in_stage_bytes = P.resize_on ? 0 : work_bytes;
   return 0;
 }
 extern "C" int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls) {

@@ -637,13 +637,14 @@ extern "C" int mn_op_resize_tile(int src_h, int src_w, int H, int W, int* tile_h
   return 0;
 }
 
-extern "C" int mn_op_resize_u8(const unsigned char* in, unsigned char* out, void* work, int B, int src_h, int src_w, int H, int W,
-                               void* stream) {
-  begin_op();
-  if (!in || !out || !work) return fail("mn_op_resize_u8: in, out and work are required");
-  if (((uintptr_t)work & 3) != 0) return fail("mn_op_resize_u8: work must be 4-byte aligned");
+// both resize entries: index null = the plain operator
+static int op_resize_u8(const char* name, const unsigned char* in, const int32_t* index, int64_t store_frames, unsigned char* out,
+                        void* work, int B, int src_h, int src_w, int H, int W, float* bad_flag, void* stream) {
+  const std::string who(name);
+  if (!in || !out || !work) return fail(who + ": in, out and work are required");
+  if (((uintptr_t)work & 3) != 0) return fail(who + ": work must be 4-byte aligned");
   const ResizePlan rp = resize_plan(B, src_h, src_w, H, W, (int*)work);
-  if (!rp.error.empty()) return fail("mn_op_resize_u8: " + rp.error);
+  if (!rp.error.empty()) return fail(who + ": " + rp.error);
   ResizeStage& st = g_resize_stage;
   const size_t bytes = rp.tables.size() * sizeof(int);
   if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) return check_launch("resize_u8 (event)");
@@ -662,8 +663,35 @@ extern "C" int mn_op_resize_u8(const unsigned char* in, unsigned char* out, void
   hipMemcpyAsync(work, st.host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
   hipEventRecord(st.ev, (hipStream_t)stream);
   st.pending = true;
-  launch_resize_u8(in, out, rp.g, (hipStream_t)stream);
+  if (index && bad_flag) hipMemsetAsync(bad_flag, 0, sizeof(float), (hipStream_t)stream);
+  launch_resize_u8(in, out, rp.g, (hipStream_t)stream, index, (long)store_frames, bad_flag);
   return check_launch("resize_u8");
+}
+
+extern "C" int mn_op_resize_u8(const unsigned char* in, unsigned char* out, void* work, int B, int src_h, int src_w, int H, int W,
+                               void* stream) {
+  begin_op();
+  return op_resize_u8("mn_op_resize_u8", in, nullptr, 0, out, work, B, src_h, src_w, H, W, nullptr, stream);
+}
+
+extern "C" int mn_op_resize_u8_indexed(const unsigned char* store, const int32_t* index, int64_t store_frames, unsigned char* out,
+                                       void* work, int B, int src_h, int src_w, int H, int W, float* bad_flag, void* stream) {
+  begin_op();
+  if (!index || ((uintptr_t)index & 3) != 0) return fail("mn_op_resize_u8_indexed: index (device int32 [B], 4-byte aligned) is required");
+  if (store_frames < 1) return fail("mn_op_resize_u8_indexed: store_frames must be at least 1");
+  return op_resize_u8("mn_op_resize_u8_indexed", store, index, store_frames, out, work, B, src_h, src_w, H, W, bad_flag, stream);
+}
+
+extern "C" int mn_op_gather_frames(const void* store, const int32_t* index, void* out, int64_t frame_bytes, int images,
+                                   int64_t store_frames, float* bad_flag, void* stream) {
+  begin_op();
+  if (!store || !out) return fail("mn_op_gather_frames: store and out are required");
+  if (!index || ((uintptr_t)index & 3) != 0) return fail("mn_op_gather_frames: index (device int32 [images], 4-byte aligned) is required");
+  const std::string err = gather_frames_error((long)frame_bytes, images, (long)store_frames);
+  if (!err.empty()) return fail("mn_op_gather_frames: " + err);
+  if (bad_flag) hipMemsetAsync(bad_flag, 0, sizeof(float), (hipStream_t)stream);
+  launch_gather_frames(store, index, out, (long)frame_bytes, images, (long)store_frames, bad_flag, (hipStream_t)stream);
+  return check_launch("gather_frames");
 }
 
 extern "C" int mn_op_stem_dgrad(int dtype, const void* gy, const void* w, float* gx, int B, int H, int W, float alpha, void* stream) {

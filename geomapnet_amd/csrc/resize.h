@@ -14,6 +14,8 @@
 // intermediate, (3) runs the vertical pass from that into an LDS image of the output rows with the skew of their global
 // addresses, and (4) stores it as 16-byte pieces, the ragged ends of a row as dwords and bytes.  The [B][sh][W][3] intermediate
 // never leaves LDS; source bytes are read once plus the tile halo.  No atomics, no scratch memory.
+// With an index (mn_set_input_index, mn_op_resize_u8_indexed) the input is a frame store and image b reads frame index[b] of it: the
+// batch is gathered by the resample itself; without one every address is what it was.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -22,6 +24,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gather.h"
 
 namespace mn {
 
@@ -172,7 +175,8 @@ __device__ __forceinline__ unsigned resize_clip8(int acc) {
 
 template <int LDS>
 static __global__ void __launch_bounds__(256) resize_u8_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
-                                                               ResizeGeom g) {
+                                                               ResizeGeom g, const int32_t* __restrict__ index, long store_frames,
+                                                               float* bad) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS];
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * g.tw, y0 = blockIdx.y * g.th, b = blockIdx.z;
@@ -190,8 +194,12 @@ static __global__ void __launch_bounds__(256) resize_u8_kernel(const unsigned ch
   // the band of source rows [r0, r0 + SR) and columns [c0, c0 + len / 3): bounds are monotone, first and last output decide
   const int c0 = g.hb[x0 * 2], len = (g.hb[(x0 + tw - 1) * 2] + g.hb[(x0 + tw - 1) * 2 + 1] - c0) * 3;
   const int r0 = g.vb[y0 * 2], SR = g.vb[(y0 + th - 1) * 2] + g.vb[(y0 + th - 1) * 2 + 1] - r0;
-  const uintptr_t in_lo = (uintptr_t)in, in_hi = in_lo + (uintptr_t)((long)g.B * g.sh * g.sw * 3);
-  const uintptr_t band = in_lo + (uintptr_t)((((long)b * g.sh + r0) * g.sw + c0) * 3);  // first byte of the band's first row
+  // the source frame: image b of the batch, or -- gathered from a frame store (mn_set_input_index) -- frame index[b] of
+  // `store_frames`; an index outside the store reads frame 0 and sets *bad (gather.h)
+  const long frames = index ? store_frames : (long)g.B;
+  const long sb = index ? checked_frame(index, b, store_frames, bad, blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) : (long)b;
+  const uintptr_t in_lo = (uintptr_t)in, in_hi = in_lo + (uintptr_t)(frames * g.sh * g.sw * 3);
+  const uintptr_t band = in_lo + (uintptr_t)(((sb * g.sh + r0) * g.sw + c0) * 3);  // first byte of the band's first row
   const long row_bytes = (long)g.sw * 3;
 
   // (1) source rows -> LDS, 16-byte pieces at their global alignment; a piece that leaves the input buffer is read by bytes
@@ -341,12 +349,14 @@ inline int64_t resize_table_bytes(int sh, int sw, int H, int W) {
   return ((int64_t)W * (2 + ksh) + (int64_t)H * (2 + ksv)) * 4;
 }
 
-inline void launch_resize_u8(const unsigned char* in, unsigned char* out, const ResizeGeom& g, hipStream_t s) {
+// index null: in = the batch [B][sh][sw][3]; else in = a frame store [store_frames][sh][sw][3] and image b reads frame index[b]
+inline void launch_resize_u8(const unsigned char* in, unsigned char* out, const ResizeGeom& g, hipStream_t s,
+                             const int32_t* index = nullptr, long store_frames = 0, float* bad = nullptr) {
   const dim3 grid(cdiv(g.W, g.tw), cdiv(g.H, g.th), g.B);
   if (g.lds_bytes <= kResizeLdsSmall)
-    hipLaunchKernelGGL((resize_u8_kernel<kResizeLdsSmall>), grid, dim3(256), 0, s, in, out, g);
+    hipLaunchKernelGGL((resize_u8_kernel<kResizeLdsSmall>), grid, dim3(256), 0, s, in, out, g, index, store_frames, bad);
   else
-    hipLaunchKernelGGL((resize_u8_kernel<kResizeLdsLarge>), grid, dim3(256), 0, s, in, out, g);
+    hipLaunchKernelGGL((resize_u8_kernel<kResizeLdsLarge>), grid, dim3(256), 0, s, in, out, g, index, store_frames, bad);
 }
 
 }  // namespace mn

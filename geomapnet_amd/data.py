@@ -166,6 +166,21 @@ class MF(torch.utils.data.Dataset):
             _, poses = self._frames(self.gt_dset, [self.dset.gt_idx[i] for i in idx])
         return imgs, torch.cat((poses, vos), dim=0)
 
+    def index_item(self, index):
+        """`__getitem__` without the images: (store indices of the window's frames [steps] int32, the same target).  For frame
+        datasets that carry `poses` [L, 6] -- resident.ResidentFrames views, whose `base` is the offset of their first frame in
+        the store -- so no frame is touched; the gaps of a variable_skip window come from the same single `get_indices` call, so
+        under the same numpy seed both select the same frames."""
+        idx = self.get_indices(index)
+        frames = torch.as_tensor(getattr(self.dset, "base", 0) + idx, dtype=torch.int32)
+        poses = torch.stack([self.dset.poses[int(i)] for i in idx], dim=0)
+        if not self.include_vos:
+            return frames, poses
+        vos = self.vo_func(poses.unsqueeze(0))[0]
+        if self.real:
+            poses = torch.stack([self.gt_dset.poses[int(self.dset.gt_idx[i])] for i in idx], dim=0)
+        return frames, torch.cat((poses, vos), dim=0)
+
     def __len__(self):
         return len(self.dset) - ((self.steps - 1) * self.skip if self.no_duplicates else 0)
 
@@ -188,6 +203,13 @@ class MFOnline(torch.utils.data.Dataset):
         # unl_targets = [absolute poses | VOs] (or absolute poses only in gps_mode): MapNet++ keeps the VO part
         tail = unl_targets if self.gps_mode else unl_targets[unl_images.shape[0]:]
         return torch.cat((lab_images, unl_images)), torch.cat((lab_poses, tail))
+
+    def index_item(self, idx):
+        """`__getitem__` without the images: (store indices [2 * steps], the same target); see MF.index_item"""
+        lab_frames, lab_poses = self.train_set.index_item(idx % len(self.train_set))
+        unl_frames, unl_targets = self.val_set.index_item(idx % len(self.val_set))
+        tail = unl_targets if self.gps_mode else unl_targets[unl_frames.shape[0]:]
+        return torch.cat((lab_frames, unl_frames)), torch.cat((lab_poses, tail))
 
     def __len__(self):
         return len(self.val_set)

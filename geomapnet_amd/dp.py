@@ -182,7 +182,8 @@ def _staged_step(engine, plan, images, targets, lib, h, s):
     import ctypes as C
     poses = plan["poses"]
     engine._jitter_pass(plan)
-    lib.check(lib.train_forward_loss(h, ptr(images), ptr(targets), ptr(plan["loss"]), ptr(poses), s))
+    with engine._input(plan, images) as base:  # (the backward stages read the network's own copy of the input)
+        lib.check(lib.train_forward_loss(h, ptr(base), ptr(targets), ptr(plan["loss"]), ptr(poses), s))
     engine._jitter_passed(plan)
     grads = engine.grads()
     works = []

@@ -4,6 +4,7 @@ PyTorch tensors are used purely as containers for HBM (parameter arena, optimise
 BatchNorm buffers, per-plan work arena) and as the source of the current HIP stream; all
 arithmetic happens in libmapnet_hip.so.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -12,6 +13,7 @@ import torch
 
 from . import _binding
 from ._binding import Config, MapNetHipError, ptr
+from .resident import IndexedFrames
 
 MODE_POSENET, MODE_MAPNET, MODE_ONLINE, MODE_GPS = 0, 1, 2, 3
 # "fp32x3": fp32 tensors exactly as "fp32", every convolution contracted on the f16 / bf16 matrix pipe with operands
@@ -384,6 +386,49 @@ class Engine:
         n = plan["images"] * cfg.H * cfg.W * 3
         return plan["resize_work"][:n].view(plan["images"], cfg.H, cfg.W, 3).clone()
 
+    # -- frames gathered from a device-resident store (resident.IndexedFrames; include/mapnet_hip.h mn_set_input_index) ----------
+    def set_input_index(self, p, frames):
+        """plan `p` reads its next passes' frames from `frames.store` through `frames.index`.  The staging buffer of the gathered
+        batch is allocated once per plan (none with the device Resize on: the resample reads the store itself)."""
+        store, cfg = frames.store, p["cfg"]
+        if store.device != self.device:
+            raise MapNetHipError("the frame store is on %s but the model on %s" % (store.device, self.device))
+        u8 = self.input_u8 is not None
+        want = (tuple(p.get("src", (cfg.H, cfg.W))) + (3,), torch.uint8) if u8 else ((3, cfg.H, cfg.W), torch.float32)
+        if (tuple(store.shape[1:]), store.dtype) != want:
+            raise MapNetHipError("the store holds %s frames of %s, the plan reads %s frames of %s"
+                                 % (store.dtype, list(store.shape[1:]), want[1], list(want[0])))
+        if frames.index.numel() != p["images"]:
+            raise MapNetHipError("%d indices for a plan of %d images" % (frames.index.numel(), p["images"]))
+        stage, nbytes = None, 0
+        if "src" not in p:
+            nbytes = int(self.lib.input_index_bytes(C.byref(cfg), int(u8)))
+            stage = p.get("index_stage")
+            if stage is None or stage.numel() != nbytes:
+                stage = p["index_stage"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.lib.check(self.lib.set_input_index(p["handle"], ptr(frames.index), int(store.shape[0]), ptr(stage), nbytes))
+
+    def clear_input_index(self, p):
+        self.lib.check(self.lib.set_input_index(p["handle"], None, 0, None, 0))
+
+    @contextlib.contextmanager
+    def _input(self, p, images):
+        """-> what the library takes as `images` for this call: the tensor itself, or -- for IndexedFrames -- the store's base with
+        the plan's index set for exactly this call (a plan never keeps a pointer past it)"""
+        if not isinstance(images, IndexedFrames):
+            yield images
+            return
+        self.set_input_index(p, images)
+        try:
+            yield images.store
+        finally:
+            self.clear_input_index(p)
+
+    def input_index_bad(self, p):
+        """1.0 if an index of the plan's last indexed pass lay outside the store (that image read frame 0), else 0.0; waits for
+        the device"""
+        return float(self.debug_tensor(p, "input_index_bad")[0].item())
+
     def image_dims(self, images):
         """-> (H, W) of one frame as the network sees it, for either input format (with the device Resize on: the plan's dims, from
         the frames' own); validates the dtype against the configured format"""
@@ -399,13 +444,14 @@ class Engine:
         return int(images.shape[-2]), int(images.shape[-1])
 
     def forward(self, images, training):
-        """images: fp32 [B,3,H,W] (or uint8 [B,H,W,3]) contiguous on the engine's device -> poses [B,6]."""
+        """images: fp32 [B,3,H,W] (or uint8 [B,H,W,3]) contiguous on the engine's device, or IndexedFrames -> poses [B,6]."""
         B = images.shape[0]
         H, W = self.image_dims(images)
         p = self.plan(MODE_POSENET, B, 1, H, W, self.source_dims(images))
         out = torch.empty(B, 6, dtype=torch.float32, device=self.device)
         self._jitter_pass(p)
-        self.lib.check(self.lib.forward(p["handle"], ptr(images), ptr(out), int(bool(training)), _stream(images)))
+        with self._input(p, images) as base:
+            self.lib.check(self.lib.forward(p["handle"], ptr(base), ptr(out), int(bool(training)), _stream(images)))
         self._jitter_passed(p)
         return out
 
@@ -433,7 +479,8 @@ class Engine:
         gx = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
         poses = torch.empty(B, 6, dtype=torch.float32, device=self.device)
         maps = torch.empty(B, H, W, dtype=torch.float32, device=self.device) if saliency else None
-        self.lib.check(self.lib.input_grad(p["handle"], ptr(x), ptr(cot), ptr(gx), ptr(maps), ptr(poses), _stream(x)))
+        with self._input(p, x) as base:
+            self.lib.check(self.lib.input_grad(p["handle"], ptr(base), ptr(cot), ptr(gx), ptr(maps), ptr(poses), _stream(x)))
         if p["dtype"] in SCALED_DTYPES and bool(self.debug_tensor(p, "input_grad_nonfinite")[0].item() != 0.0):
             # not a skipped step: nothing was trained.  The caller lowers the loss scale (set_compute_dtype / Engine.loss_scale)
             raise MapNetHipError("input_grad: the %s gradient is not finite at loss scale %g; lower the loss scale or use fp32"
@@ -492,14 +539,15 @@ class Engine:
         side = self.step_stream()
         self._jitter_pass(p)
         if side is None:
-            self.lib.check(self.lib.train_step(p["handle"], ptr(images), ptr(targets), ptr(p["loss"]), ptr(p["poses"]), None))
+            with self._input(p, images) as base:
+                self.lib.check(self.lib.train_step(p["handle"], ptr(base), ptr(targets), ptr(p["loss"]), ptr(p["poses"]), None))
             self._jitter_passed(p)
             self._stepped(p)
             return p["loss"], p["poses"].clone()
         cur = torch.cuda.current_stream(self.device)
         side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            self.lib.check(self.lib.train_step(p["handle"], ptr(images), ptr(targets), ptr(p["loss"]), ptr(p["poses"]),
+        with torch.cuda.stream(side), self._input(p, images) as base:
+            self.lib.check(self.lib.train_step(p["handle"], ptr(base), ptr(targets), ptr(p["loss"]), ptr(p["poses"]),
                                                C.c_void_p(side.cuda_stream)))
             poses = p["poses"].clone()
         cur.wait_stream(side)

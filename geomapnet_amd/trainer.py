@@ -75,7 +75,10 @@ def read_config(config_file):
 
 class Trainer:
     def __init__(self, model, optimizer, train_criterion, config_file, experiment, train_dataset, val_dataset, device,
-                 checkpoint_file=None, resume_optim=False, val_criterion=None, logdir=None, log=print):
+                 checkpoint_file=None, resume_optim=False, val_criterion=None, logdir=None, log=print, resident=False):
+        """resident=True: the frames of the training and validation sets are uploaded once into one device tensor and every batch
+        is gathered from it by index (resident.py): the loaders yield (IndexedFrames, target) in the host loaders' order.  Under
+        data parallel every rank holds the full store and the DistributedSampler stays."""
         self.model = model
         self.train_criterion = train_criterion
         self.val_criterion = train_criterion if val_criterion is None else val_criterion
@@ -115,17 +118,31 @@ class Trainer:
         if dp.world_size() > 1:
             self.train_sampler = torch.utils.data.distributed.DistributedSampler(
                 train_dataset, shuffle=self.config["shuffle"], seed=self.config["seed"], drop_last=True)
-        self.train_loader = torch.utils.data.DataLoader(
-            train_dataset, batch_size=self.config["batch_size"],
-            shuffle=self.config["shuffle"] and self.train_sampler is None, sampler=self.train_sampler,
-            num_workers=self.config["num_workers"], pin_memory=pin, collate_fn=safe_collate,
-            drop_last=dp.world_size() > 1)  # equal local batches: the gradient mean over ranks needs them
-        if self.config["do_val"]:
-            self.val_loader = torch.utils.data.DataLoader(
-                val_dataset, batch_size=self.config["batch_size"], shuffle=self.config["shuffle"],
-                num_workers=self.config["num_workers"], pin_memory=pin, collate_fn=safe_collate)
+        self.frame_store = None
+        self.val_loader = None
+        if not resident:
+            self.train_loader = torch.utils.data.DataLoader(
+                train_dataset, batch_size=self.config["batch_size"],
+                shuffle=self.config["shuffle"] and self.train_sampler is None, sampler=self.train_sampler,
+                num_workers=self.config["num_workers"], pin_memory=pin, collate_fn=safe_collate,
+                drop_last=dp.world_size() > 1)  # equal local batches: the gradient mean over ranks needs them
+            if self.config["do_val"]:
+                self.val_loader = torch.utils.data.DataLoader(
+                    val_dataset, batch_size=self.config["batch_size"], shuffle=self.config["shuffle"],
+                    num_workers=self.config["num_workers"], pin_memory=pin, collate_fn=safe_collate)
         else:
-            self.val_loader = None
+            from .resident import ResidentLoader, make_resident
+            dev = torch.device("cuda", torch.cuda.current_device()) if self.config["cuda"] else torch.device("cpu")
+            sets = [train_dataset] + ([val_dataset] if self.config["do_val"] else [])
+            sets, self.frame_store = make_resident(sets, dev)
+            nbytes = self.frame_store.numel() * self.frame_store.element_size()
+            self._log("Resident frame store: {:d} frames, {:.1f} MB on {:s}".format(self.frame_store.shape[0], nbytes / 1e6, str(dev)))
+            self.train_loader = ResidentLoader(
+                sets[0], batch_size=self.config["batch_size"], shuffle=self.config["shuffle"] and self.train_sampler is None,
+                sampler=self.train_sampler, drop_last=dp.world_size() > 1, device=dev)
+            if self.config["do_val"]:
+                self.val_loader = ResidentLoader(sets[1], batch_size=self.config["batch_size"], shuffle=self.config["shuffle"],
+                                                 device=dev)
 
         if self.config["cuda"]:
             self.model.cuda()
@@ -136,6 +153,8 @@ class Trainer:
         self.prefetch = self.config["cuda"] and os.environ.get("MN_PREFETCH", "1") != "0"
 
     def _feed(self, loader):
+        if self.frame_store is not None:  # a ResidentLoader feeds its index and target batches itself
+            return loader
         return DeviceFeed(loader, engine_of(self.model).device) if self.prefetch else loader
 
     def save_checkpoint(self, epoch):

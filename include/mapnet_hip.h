@@ -236,6 +236,26 @@ int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls);
 int64_t mn_input_resize_bytes(const mn_config* cfg, int src_h, int src_w);
 int mn_set_input_resize(mn_handle* h, int src_h, int src_w, void* work, int64_t work_bytes);
 
+/* Batches gathered by index from a device-resident frame store: replaces the batch assembly of the reference's host loader -- the
+ * DataLoader + default_collate of common/train.py:180-188 and the torch.stack of MF.__getitem__, dataset_loaders/composite.py:77-83 --
+ * for sequences that were uploaded once.  mn_set_input_index: index_dev is device int32 [images] (4-byte aligned); while it is set,
+ * the `images` argument of mn_forward / mn_train_step / mn_train_forward_loss / mn_input_grad is the BASE of the store --
+ * [store_frames][src_h | H][src_w | W][3] uint8 (source sized when mn_set_input_resize is on) or [store_frames][3][H][W] fp32 -- and
+ * image b of the batch is frame index_dev[b] of it.  The index is read by the kernels when a pass runs, so the caller may rewrite
+ * its contents, stream-ordered, between passes.  With the resize on, the resample reads its source frames through the index and
+ * `work` is ignored (no staging: pass NULL, 0); otherwise one copy kernel gathers the batch into `work` (mn_input_index_bytes:
+ * images * 3 * H * W bytes, x 4 for fp32 input; -1 on a bad cfg) at the head of the pass.  mn_input_index_bytes sees the config
+ * alone, not the handle: for a plan whose mn_set_input_resize is on its value means nothing -- that plan needs 0 bytes.  Everything
+ * downstream -- the uint8 / fp32 input conversion, the ColorJitter chain with its contrast mean, the x of mn_input_grad's saliency
+ * map -- reads the gathered batch where it read `images`.  An index outside [0, store_frames) never becomes an address: that image
+ * reads frame 0 and the float behind mn_debug_tensor "input_index_bad", cleared at the head of every indexed pass, is set to 1.
+ * The call only records pointers: it does not wait for the device and launches nothing; mn_plan_bytes and the work arena are
+ * unchanged, and a plan with no index set launches exactly what it launched before.  index_dev = NULL turns indexing off (the other
+ * arguments are ignored).  `work` and `index_dev` must stay valid until indexing is turned off.  Fails on store_frames < 1, a NULL or
+ * too small `work` where staging is needed, a misaligned index_dev. */
+int64_t mn_input_index_bytes(const mn_config* cfg, int input_u8);
+int mn_set_input_index(mn_handle* h, const int32_t* index_dev, int64_t store_frames, void* work, int64_t work_bytes);
+
 /* Attention maps: replaces `data_var = Variable(data, requires_grad=True); pose = model(data_var); pose.mean().backward();
  * data_var.grad` of scripts/plot_activations.py:117-123, with model.eval() (plot_activations.py:50).  Runs the eval forward pass
  * and the data-gradient chain alone: BatchNorm on running statistics (a per-channel scale), no weight gradients, no optimiser.
@@ -502,6 +522,17 @@ int mn_op_color_jitter(const unsigned char* in, float* out, float* draws, float*
 int mn_op_resize_u8(const unsigned char* in, unsigned char* out, void* work, int B, int src_h, int src_w, int H, int W, void* stream);
 int64_t mn_op_resize_work_bytes(int src_h, int src_w, int H, int W);
 int mn_op_resize_tile(int src_h, int src_w, int H, int W, int* tile_h, int* tile_w);
+
+/* the gather of mn_set_input_index on its own (default_collate / torch.stack of the reference's host loader, common/train.py:180-188,
+ * dataset_loaders/composite.py:77-83): out[b] = store[index[b]] for b < images <= 65535, frames as opaque rows of frame_bytes bytes
+ * (any positive size; store and out at any byte alignment; frame offsets are 64-bit), index device int32 [images].  bad_flag (device
+ * float, may be NULL) is cleared ahead of the kernel and set to 1 if an index lies outside [0, store_frames): that image reads
+ * frame 0.  mn_op_resize_u8_indexed: mn_op_resize_u8 whose image b is resampled from frame index[b] of a store
+ * [store_frames][src_h][src_w][3], with the same flag. */
+int mn_op_gather_frames(const void* store, const int32_t* index, void* out, int64_t frame_bytes, int images, int64_t store_frames,
+                        float* bad_flag, void* stream);
+int mn_op_resize_u8_indexed(const unsigned char* store, const int32_t* index, int64_t store_frames, unsigned char* out, void* work,
+                            int B, int src_h, int src_w, int H, int W, float* bad_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (no counterpart in the reference, which is single-device: common/train.py:91-92).

@@ -74,6 +74,11 @@ def build_parser():
                         help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
                              "transform, scripts/train.py:120): the dataset yields frames of --height x --width and the network runs "
                              "at the resized size; needs --u8_input")
+    parser.add_argument("--resident_frames", action="store_true",
+                        help="upload the training and validation frames once into one device tensor and gather every batch from "
+                             "it by index on the device (geomapnet_amd/resident.py) instead of stacking frames on the host every "
+                             "step; the batch order is the host loader's.  Works with or without --u8_input, --device_resize, "
+                             "--device_color_jitter; the store must fit the device's free memory")
     kinds = ("l1", "mse", "smooth_l1", "huber", "quaternion")
     parser.add_argument("--t_loss_fn", choices=kinds, default="l1",
                         help="the training criterion's t_loss_fn (common/criterion.py:34,55,112; the reference's scripts pass "
@@ -242,7 +247,7 @@ def run(args, datasets=None, _binding=None, log=print):
     experiment_name += args.suffix
     trainer = Trainer(model, optimizer, train_criterion, settings, experiment_name, train_set, val_set, device=args.device,
                       checkpoint_file=args.checkpoint, resume_optim=args.resume_optim, val_criterion=val_criterion,
-                      logdir=args.logdir, log=log)
+                      logdir=args.logdir, log=log, resident=args.resident_frames)
     trainer.train_val(lstm=False)
     return trainer
 
