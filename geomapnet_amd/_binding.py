@@ -63,6 +63,7 @@ _PROTOS = {
     "mn_set_color_jitter_calls": (c_i, [c_void, C.c_uint32]),
     "mn_input_resize_bytes": (c_i64, [C.POINTER(Config), c_i, c_i]),
     "mn_set_input_resize": (c_i, [c_void, c_i, c_i, c_void, c_i64]),
+    "mn_set_eval_fused": (c_i, [c_void, c_i]),
     "mn_input_index_bytes": (c_i64, [C.POINTER(Config), c_i]),
     "mn_set_input_index": (c_i, [c_void, c_void, c_i64, c_void, c_i64]),
     "mn_forward": (c_i, [c_void, c_void, c_void, c_i, c_void]),
@@ -81,6 +82,7 @@ _PROTOS = {
     "mn_op_igemm": (c_i, [c_i, C.POINTER(GatherGeom), c_void, c_void, c_void, c_i, c_void, c_void, c_i, c_void, c_void,
                           c_f, c_void, c_void]),
     "mn_op_igemm_grid_m": (c_i, [c_i]),
+    "mn_op_conv_bn_eval": (c_i, [c_i, C.POINTER(GatherGeom), c_void, c_void, c_void, c_void, c_i, c_void, c_i, c_void, c_void]),
     "mn_op_wgrad": (c_i, [c_i, C.POINTER(GatherGeom), c_void, c_i, c_void, c_void, c_i, c_void, c_f, c_i, c_void, c_void]),
     "mn_op_wgrad_ws_floats": (c_i64, []),
     "mn_op_wgrad_ws": (c_i, [c_i, C.POINTER(GatherGeom), c_void, c_i, c_void, c_void, c_i, c_f, c_void, c_i64, c_void, c_void]),

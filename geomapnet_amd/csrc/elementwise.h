@@ -162,6 +162,34 @@ __device__ __forceinline__ void bn_rows_sum(const double* __restrict__ accum, in
   __syncthreads();
 }
 
+// (mean, var) of channel c -> coef[0][c] = gamma * invstd, coef[1][c] = beta - mean * scale, and mean / invstd published: the tail
+// of bn_finalize_fwd_kernel, and with the running statistics all of bn_eval_coef_all_kernel
+__device__ __forceinline__ void bn_write_coef(const BnParams& p, int c, float mean, float var, float* __restrict__ coef, int C) {
+  const float invstd = 1.0f / sqrtf(var + p.eps);
+  const float sc = p.gamma[c] * invstd;
+  coef[c] = sc;
+  coef[C + c] = p.beta[c] - mean * sc;
+  p.mean[c] = mean;
+  p.invstd[c] = invstd;
+}
+
+// The inference coefficients of EVERY BatchNorm of a network in one launch (the fused inference pass, net.hip): a device job table
+// built at plan creation, one workgroup per job and 256 channels.  It runs at the head of every such pass -- the running statistics,
+// gamma and beta are read where the optimiser and the caller (the buffers are the caller's memory) leave them, so no flag can let coefficients go stale.
+struct BnEvalJob {
+  BnParams p;
+  float* coef;  // [2][C]
+  int C;
+};
+constexpr int kBnEvalChunks = 2;  // workgroups per job: C <= 512
+static __global__ void __launch_bounds__(256) bn_eval_coef_all_kernel(const BnEvalJob* __restrict__ jobs, int njobs) {
+  const int j = blockIdx.x / kBnEvalChunks;
+  if (j >= njobs) return;
+  const BnEvalJob job = jobs[j];
+  const int c = (blockIdx.x % kBnEvalChunks) * 256 + threadIdx.x;
+  if (c < job.C) bn_write_coef(job.p, c, job.p.running_mean[c], job.p.running_var[c], job.coef, job.C);
+}
+
 static __global__ void __launch_bounds__(256) bn_finalize_fwd_kernel(const double* __restrict__ accum, double count, BnParams p,
                                                                      int training, float* __restrict__ coef, int C,
                                                                      int accum_rows) {
@@ -184,12 +212,7 @@ static __global__ void __launch_bounds__(256) bn_finalize_fwd_kernel(const doubl
       mean = p.running_mean[c];
       var = p.running_var[c];
     }
-    const float invstd = 1.0f / sqrtf(var + p.eps);
-    const float sc = p.gamma[c] * invstd;
-    coef[c] = sc;
-    coef[C + c] = p.beta[c] - mean * sc;
-    p.mean[c] = mean;
-    p.invstd[c] = invstd;
+    bn_write_coef(p, c, mean, var, coef, C);
     if (training) {
       p.running_mean[c] = (1.f - p.momentum) * p.running_mean[c] + p.momentum * mean;
       p.running_var[c] = (1.f - p.momentum) * p.running_var[c] + p.momentum * (float)unbiased;

@@ -10,22 +10,7 @@
 
 namespace mn {
 
-// 8 channels c .. c + 7 (c % 8 == 0) of row `row`: the hi piece sits at half index h2_index(row, C, c), the lo piece 32 halves on
-__device__ __forceinline__ void h2_store8(half* __restrict__ base, long row, int C, int c, const float (&x)[8]) {
-  PieceView<half> hi, lo;
-  split8_f16(x, hi.v, lo.v);
-  half* p = base + h2_index(row, C, c);
-  *reinterpret_cast<piece_t*>(p) = hi.p;
-  *reinterpret_cast<piece_t*>(p + 32) = lo.p;
-}
-__device__ __forceinline__ void h2_load8(const half* __restrict__ base, long row, int C, int c, float (&x)[8]) {
-  const half* p = base + h2_index(row, C, c);
-  PieceView<half> hi, lo;
-  hi.p = *reinterpret_cast<const piece_t*>(p);
-  lo.p = *reinterpret_cast<const piece_t*>(p + 32);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) x[e] = (float)hi.e[e] + (float)lo.e[e];
-}
+// (h2_store8 / h2_load8 -- 8 channels of an h2 row -- live in common.h: the fused inference epilogues of the convolutions use them too)
 
 // ---- h2q (common.h): fp16 hi halves where h2 has them, the lo halves and a copy of the hi halves as fp8 with fixed exponents ----
 // four floats -> four fp8 e4m3 bytes (saturating at +-448)

@@ -48,7 +48,12 @@ inline bool conv_halo_h2_applies(const GatherGeom& g, const Epilogue& ep) {
 // PD: K sub-steps a B fragment is requested ahead of its MFMAs.  SG: 0 = a step's reads and its MFMAs as two fenced blocks (first
 // version), 1 = the scheduler is asked to interleave them (sched_group_barrier: it moves every read right in front of its use),
 // 2 = interleaved by hand: one read (or one DMA of the next halo) behind each MFMA.
-template <bool STATS, int ABL = 0, int PD = 1, int SG = 2>
+// EV (with STATS = false): the fused inference epilogue (igemm.h Epilogue::bn_coef).  A lane's accumulator quad is 4 consecutive
+// channels of one pixel, so the finished h2 activation leaves as an 8-byte piece of hi halves and an 8-byte piece of lo halves per
+// quad (the unfused form: one 16-byte fp32 piece), the h2 residual is read in the same pattern, and the lane's 16 (scale, shift)
+// pairs sit in the 32 registers the STATS = false instantiation does not spend on st1 / st2.  The arithmetic is
+// bn_apply_h2_kernel's in its order; two quads share one split8_f16, so the halves are the ones h2_store8 would write.
+template <bool STATS, int ABL = 0, int PD = 1, int SG = 2, bool EV = false>
 static __global__ void __launch_bounds__(256, 1) conv_halo_h2_kernel(GatherGeom g, const half* __restrict__ A,
                                                                      const half* __restrict__ Bw, Epilogue ep, int tiles_x,
                                                                      int tiles_y, int ntiles) {
@@ -67,7 +72,10 @@ static __global__ void __launch_bounds__(256, 1) conv_halo_h2_kernel(GatherGeom 
   const float alpha = ep.alpha;
 
   const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(A, (long)g.B * g.Hi * g.Wi * 256L);
-  const __amdgpu_buffer_rsrc_t rsrc_out = make_rsrc(ep.out, (long)g.B * g.P * g.Q * 64L * 4L);
+  const __amdgpu_buffer_rsrc_t rsrc_out = make_rsrc(ep.out, (long)g.B * g.P * g.Q * 64L * 4L);  // (fp32 or h2: 4 bytes per element)
+  static_assert(!EV || !STATS, "EV: no column sums");
+  const bool has_res = EV && ep.bn_res != nullptr;
+  const __amdgpu_buffer_rsrc_t rsrc_res = make_rsrc(EV ? ep.bn_res : nullptr, has_res ? (long)g.B * g.P * g.Q * 64L * 4L : 0L);
 
   // ---- this wave's weights: A operands of v_mfma_f32_32x32x16_f16 (lane: output channel ch * 32 + (lane & 31), k = 8 * (lane >> 5)
   //      .. + 7 of a 16-k sub-step).  Piece i = tap * 4 + g * 2 + s: tap, 32-channel group g, 16-k half s of the group.
@@ -119,6 +127,20 @@ static __global__ void __launch_bounds__(256, 1) conv_halo_h2_kernel(GatherGeom 
   if constexpr (STATS) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) st1[r] = st2[r] = 0.f;
+  }
+  float bsc[EV ? 16 : 1], bsh[EV ? 16 : 1];  // EV: (scale, shift) of accumulator register r = channel ch * 32 + 8 (r >> 2) + 4 kh + (r & 3)
+  if constexpr (EV) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      PieceView<float> a, b;
+      a.p = *reinterpret_cast<const piece_t*>(ep.bn_coef + ch * 32 + 8 * q + 4 * kh);
+      b.p = *reinterpret_cast<const piece_t*>(ep.bn_coef + 64 + ch * 32 + 8 * q + 4 * kh);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bsc[q * 4 + e] = a.e[e];
+        bsh[q * 4 + e] = b.e[e];
+      }
+    }
   }
 
   // fragment addressing: pixel block bb of this wave = tile rows (ph * 2 + bb) * 2, + 1; lane = pixel (l31 >> 4, l31 & 15)
@@ -238,6 +260,42 @@ static __global__ void __launch_bounds__(256, 1) conv_halo_h2_kernel(GatherGeom 
     for (int bb = 0; bb < 2; ++bb) {
       const int y = y0 + (ph * 2 + bb) * 2 + (l31 >> 4), x = x0 + col;
       const bool ok = y < gP && x < gQ;
+      if constexpr (EV) {
+        // h2 row of 64 channels = 256 bytes: group ch at byte 128 ch (64 bytes of hi halves, then 64 of lo halves); quad q of this
+        // lane = channels 8 q + 4 kh .. + 3 of the group = bytes 16 q + 8 kh of either half
+        const unsigned hoff = ok ? (unsigned)(((b * gP + y) * gQ + x) * 256 + ch * 128 + kh * 8) : kOob;
+        Half4View rh[4], rl[4];
+        if (has_res) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            rh[q].p = __builtin_amdgcn_raw_buffer_load_b64(rsrc_res, (int)hoff, q * 16, 0);
+            rl[q].p = __builtin_amdgcn_raw_buffer_load_b64(rsrc_res, (int)hoff, q * 16 + 64, 0);
+          }
+        }
+#pragma unroll
+        for (int q2 = 0; q2 < 2; ++q2) {  // quads 2 q2 and 2 q2 + 1 through one 8-wide split
+          float f[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int r = (2 * q2 + (e >> 2)) * 4 + (e & 3);
+            float v = acc[bb][r] * alpha;
+            v = v * bsc[r] + bsh[r];
+            if (has_res) v += (float)rh[r >> 2].e[r & 3] + (float)rl[r >> 2].e[r & 3];
+            if (ep.bn_relu) v = fmaxf(v, 0.f);
+            f[e] = v;
+          }
+          PieceView<half> hi, lo;
+          split8_f16(f, hi.v, lo.v);
+          if constexpr ((ABL & 4) == 0) {
+            const u32x2 h0 = {hi.p[0], hi.p[1]}, h1 = {hi.p[2], hi.p[3]}, l0 = {lo.p[0], lo.p[1]}, l1 = {lo.p[2], lo.p[3]};
+            __builtin_amdgcn_raw_buffer_store_b64(h0, rsrc_out, (int)hoff, q2 * 32, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(l0, rsrc_out, (int)hoff, q2 * 32 + 64, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(h1, rsrc_out, (int)hoff, q2 * 32 + 16, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(l1, rsrc_out, (int)hoff, q2 * 32 + 80, 0);
+          }
+        }
+        continue;
+      }
       const unsigned voff = ok ? (unsigned)((((b * gP + y) * gQ + x) * 64 + ch * 32 + 4 * kh) * 4) : kOob;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -325,10 +383,15 @@ inline int conv_halo_h2_grid(const GatherGeom& g) {
   const int wgs = knobs().halo_h2_wgs;
   return ntiles < wgs ? ntiles : wgs;
 }
+template <bool EV>
 inline void launch_conv_halo_h2(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream) {
   const int tx = cdiv(g.Q, kH2TW), ty = cdiv(g.P, kH2TH);
   const int ntiles = g.B * tx * ty;
   const dim3 grid(conv_halo_h2_grid(g));
+  if constexpr (EV) {  // the fused inference epilogue: same tiles, same grid
+    hipLaunchKernelGGL((conv_halo_h2_kernel<false, 0, 1, 2, true>), grid, dim3(256), 0, stream, g, A, Bw, ep, tx, ty, ntiles);
+    return;
+  }
 #ifdef MN_ABLATION_BUILD
   const int abl = knobs().halo_h2_ablate;
   {

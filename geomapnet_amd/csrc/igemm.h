@@ -99,6 +99,16 @@ struct Epilogue {
   int om_on = 0, om_P = 0, om_Q = 0, om_H = 0, om_W = 0, om_a = 0, om_b = 0;
   FastDiv om_dq{0, 0}, om_dp{0, 0};
   float alpha;           // scale applied to the accumulator
+  // Fused inference epilogue (the EV instantiations of the h2 forward kernels only; off by default): the BatchNorm of an eval pass
+  // is a per-channel constant known before the convolution starts, so the accumulators leave the kernel as the FINISHED h2
+  // activation -- out(h2) = [relu](acc * scale[n] + shift[n] [+ bn_res(h2)]), bn_apply_h2_kernel's arithmetic in its order -- and
+  // no fp32 conv output exists.  bn_coef: fp32 [2][N], scale | shift (16-byte aligned, N % 8 == 0); `out` is then an h2 tensor
+  // [M][ldc].  The caller leaves every other field as the unfused launch of an inference pass has it -- stats / stats_accum / bias /
+  // res / gates null, relu 0, alpha 1: the dispatchers read them to pick the kernel, and the staging code ahead of the store passes
+  // (shared with the unfused instantiation) still applies alpha, bias and relu to the accumulators.
+  const float* bn_coef = nullptr;
+  const void* bn_res = nullptr;  // h2 residual [M][ldc] or null
+  int bn_relu = 0;
   // (Measured and removed in round 3: BatchNorm-BACKWARD sums (sum g, sum g * y of the BatchNorm that consumes the stored
   // gradient next) taken in the row-wise store passes of this epilogue and igemm_halo.h's, to drop the reduction launches
   // that read the gradient back.  The extra 16-byte load of y per stored piece sits, latency exposed, in each of the 6-12
@@ -109,6 +119,27 @@ struct Epilogue {
 struct RowDiv {
   FastDiv q, p;  // divisors GatherGeom.Q and GatherGeom.P
 };
+
+// Fused inference epilogue, one thread's share of a store pass: channels col .. col + 7 (col % 8 == 0) of output row `row`, the
+// staged accumulators in v.  The multiply-add is written as bn_apply_h2_kernel writes it, so that a build contracts both or neither.
+__device__ __forceinline__ void bn_eval_store8(const Epilogue& ep, int N, long row, int col, float (&v)[8]) {
+  PieceView<float> sc0, sc1, sh0, sh1;
+  sc0.p = *reinterpret_cast<const piece_t*>(ep.bn_coef + col);
+  sc1.p = *reinterpret_cast<const piece_t*>(ep.bn_coef + col + 4);
+  sh0.p = *reinterpret_cast<const piece_t*>(ep.bn_coef + N + col);
+  sh1.p = *reinterpret_cast<const piece_t*>(ep.bn_coef + N + col + 4);
+  const half* res = reinterpret_cast<const half*>(ep.bn_res);
+  float r[8];
+  if (res) h2_load8(res, row, ep.ldc, col, r);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float f = v[e] * (e < 4 ? sc0.e[e & 3] : sc1.e[e & 3]) + (e < 4 ? sh0.e[e & 3] : sh1.e[e & 3]);
+    if (res) f += r[e];
+    if (ep.bn_relu) f = fmaxf(f, 0.f);
+    v[e] = f;
+  }
+  h2_store8(reinterpret_cast<half*>(ep.out), row, ep.ldc, col, v);
+}
 
 template <typename T>
 __device__ __forceinline__ void mma_piece(const PieceView<T>& a, const PieceView<T>& b, floatx16& c);
@@ -221,8 +252,11 @@ __device__ __forceinline__ void wait_vmcnt() {
 // DMA issue) separated by workgroup-wide barriers, group 1 one phase late -- parity-green and 2x SLOWER (layer3 306 -> 660
 // us, whole step 40.9 -> 64.9 ms): every phase then lasts as long as the slowest of eight waves' waits.  What is left to
 // try is software pipelining INSIDE a wave (the splits of group kp + 1 in the shadow of the MFMAs of group kp).
+// EV (MM = MMA_H2 only): the fused inference epilogue (Epilogue::bn_coef) -- a store-pass thread takes 8 consecutive channels from
+// the stage and writes the finished h2 activation; no column sums, no fp32 output.  Everything ahead of the store passes is the
+// EV = false instantiation's, so the accumulators are the ones that launch would have stored.
 template <typename T, int WM, int WN, int TM, int TN, int NP, int NBUF, int MINW, bool UNI, bool SPL = false, int ABL = 0,
-          int MM = MMA_NATIVE>
+          int MM = MMA_NATIVE, bool EV = false>
 static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherGeom g, const T* __restrict__ A,
                                                                          const T* __restrict__ Bw, Epilogue ep, int grid_n,
                                                                          const T* __restrict__ zero_page, RowDiv rd) {
@@ -232,6 +266,7 @@ static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherG
   constexpr bool H2 = MM == MMA_H2 || MM == MMA_H2Q;
   constexpr bool HQ = MM == MMA_H2Q;  // h2q operands: both cross terms of a K-step in one scaled fp8 MFMA (igemm_halo.h Q)
   static_assert(!H2 || (sizeof(T) == 2 && NP == 8 && UNI), "h2: fp16 pieces, one 32-channel group per K-step");
+  static_assert(!EV || MM == MMA_H2, "EV: an h2 variant");
   constexpr int NT = WM * WN * 64;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int WTM = TM * 32, WTN = TN * 32;
@@ -706,7 +741,7 @@ static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherG
   // h2: the output (raw conv output / data gradient, consumed by the BatchNorm kernels) and the residual are fp32 [M][ldc];
   // the gates are h2 activations, of which only the hi halves are read (the sign of x is the sign of its hi half)
   using OT = typename std::conditional<H2, float, T>::type;
-  constexpr int OVEC = 16 / (int)sizeof(OT);
+  constexpr int OVEC = EV ? 8 : 16 / (int)sizeof(OT);  // channels a store-pass thread takes from the stage
   OT* out = reinterpret_cast<OT*>(ep.out);
   const OT* res = reinterpret_cast<const OT*>(ep.res);
   const T* gate = reinterpret_cast<const T*>(ep.res_gate);
@@ -737,8 +772,10 @@ static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherG
               for (int r = 0; r < 16; ++r) {
                 float v = acc[i][j][r] * alpha + bias;
                 if (ep.relu & 1) v = fmaxf(v, 0.f);
-                s1[j] += v;
-                s2[j] += v * v;
+                if constexpr (!EV) {
+                  s1[j] += v;
+                  s2[j] += v * v;
+                }
                 const int lr = (wm % WR) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 stage[lr * SC + (lc - nh * SC)] = v;
               }
@@ -769,7 +806,9 @@ static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherG
               orow = ((long)ob * ep.om_H + 2 * op + ep.om_a) * ep.om_W + 2 * oq + ep.om_b;
             }
             const long idx = orow * ep.ldc + col;
-            if constexpr (H2) {
+            if constexpr (EV) {
+              bn_eval_store8(ep, g.N, orow, col, v);
+            } else if constexpr (H2) {
               const long gidx = h2_index(orow, ep.ldc, col);  // hi halves of the gate's channels col .. col + 3
               if (res) {
                 PieceView<float> rv;
@@ -824,6 +863,7 @@ static __global__ void __launch_bounds__(WM* WN * 64, MINW) igemm_kernel(GatherG
         }
         __syncthreads();
       }
+  if constexpr (EV) return;
   if (ep.stats || ep.stats_accum) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -1019,16 +1059,23 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
 // h2 operands (common.h MMA_H2): `g_in` describes the convolution in REAL channels; A is an h2 tensor [B][Hi][Wi][C], Bw an
 // h2 weight matrix [N][taps][C] (row pitch ldb real elements), out / res fp32, gates h2.  The kernels see fp16 tensors with 2C
 // channels.  128x128 / 128x64 tiles of four waves, two workgroups per CU (3x3 stride-1 shapes go to igemm_halo.h).
+// EV (all three families): the fused inference epilogue (Epilogue::bn_coef).  The choice of kernel and tile shape is this ONE body
+// for both forms -- it reads the geometry and the epilogue fields an EV launch leaves as the unfused launch has them -- so a fused
+// launch runs the instantiation whose accumulators the unfused launch of the same geometry would have stored.  h2 operands only.
+template <bool EV = false>
 inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream);
 // q: A and Bw are h2q tensors (common.h), the cross terms run on the scaled fp8 MFMA (MMA_H2Q)
 // (halo_h2.h, round 6: layer1's 64 -> 64 h2 convolutions with the weights in registers)
 inline bool conv_halo_h2_applies(const GatherGeom& g, const Epilogue& ep);
 inline int conv_halo_h2_grid(const GatherGeom& g);
+template <bool EV = false>
 inline void launch_conv_halo_h2(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream);
+template <bool EV = false>
 inline int launch_igemm_h2(const GatherGeom& g_in, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream,
                            const half* zero_page, bool q = false) {
+  if (EV && q) return -1;  // (no fused h2q instantiations: the callers refuse)
   if (!q && conv_halo_h2_applies(g_in, ep)) {
-    launch_conv_halo_h2(g_in, A, Bw, ep, stream);
+    launch_conv_halo_h2<EV>(g_in, A, Bw, ep, stream);
     return conv_halo_h2_grid(g_in);
   }
   GatherGeom g = g_in;
@@ -1041,14 +1088,17 @@ inline int launch_igemm_h2(const GatherGeom& g_in, const half* A, const half* Bw
   rd.q = make_fastdiv(g.Q);
   rd.p = make_fastdiv(g.P);
   if (knobs().igemm_halo > 0) {
-    const int gm_halo = launch_igemm_halo_h2(g, A, Bw, ep, stream);
+    const int gm_halo = launch_igemm_halo_h2<EV>(g, A, Bw, ep, stream);
     if (gm_halo >= 0) return gm_halo;
   }
 #define MN_H2_CFG(WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_)                                                                   \
   {                                                                                                                        \
     constexpr int BM = WM_ * TM_ * 32, BN = WN_ * TN_ * 32;                                                                \
     const int gm = cdiv(g.M, BM), gn = cdiv(g.N, BN);                                                                      \
-    if (q)                                                                                                                 \
+    if constexpr (EV)                                                                                                      \
+      hipLaunchKernelGGL((igemm_kernel<half, WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_, true, false, 0, MMA_H2, true>), dim3(gm * gn), \
+                         dim3(WM_ * WN_ * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);                                \
+    else if (q)                                                                                                            \
       hipLaunchKernelGGL((igemm_kernel<half, WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_, true, false, 0, MMA_H2Q>), dim3(gm * gn), \
                          dim3(WM_ * WN_ * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);                                \
     else                                                                                                                   \

@@ -71,8 +71,10 @@ namespace mn {
 // v_mfma_scale_f32_32x32x64_f8f6f4 contracts both cross terms from the group's fp8 planes ([lo8 | hi8] of A against [hi8 | lo8] of B:
 // a lane's operand is piece 4 + half followed by piece 6 + half; scale bytes are constants of the lane half), then the two fp16
 // MFMAs of hi*hi: 128 instead of 192 matrix-pipe cycles per K-step and tile pair, the same LDS-DMA bytes and fragment reads.
+// EV (with H2, not Q): the fused inference epilogue (igemm.h Epilogue::bn_coef, igemm_kernel EV) -- in the store passes a thread
+// takes 8 consecutive channels from the stage, not 4, and writes the finished h2 activation; no column sums, no fp32 output.
 template <int BN, int kAH, int ABL = 0, int DP = 1, bool H2 = false, int WM = 3, int WN = 4, bool A1 = false,
-          int OCC = (A1 ? 2 : 1), bool Q = false>
+          int OCC = (A1 ? 2 : 1), bool Q = false, bool EV = false>
 static __global__ void __launch_bounds__(WM* WN * 64, OCC * WM* WN / 4) igemm_halo_kernel(GatherGeom g, const half* __restrict__ A,
                                                                    const half* __restrict__ Bw, Epilogue ep, int grid_n,
                                                                    RowDiv rd) {
@@ -82,6 +84,7 @@ static __global__ void __launch_bounds__(WM* WN * 64, OCC * WM* WN / 4) igemm_ha
   constexpr int NBS = 2, NIMG = A1 ? 1 : 2, A_IMG = kAH * NP, B_SLOT = BN * NP, RING = NIMG * A_IMG + NBS * B_SLOT;  // pieces
   constexpr int SC = BN < 128 ? BN : 128;  // columns staged per epilogue round
   static_assert(!Q || H2, "Q: an h2 variant");
+  static_assert(!EV || (H2 && !Q), "EV: an h2 variant");
   static_assert((RING + 1 + WM * BN / 2) * 16 <= (OCC == 2 ? 80 : 160) * 1024, "LDS");
   static_assert(RING * 16 >= WM * 32 * SC * 4, "epilogue staging (the ring is free by then)");
   constexpr int A_PASSES = (kAH + RPP - 1) / RPP, B_PASSES = (BN + RPP - 1) / RPP;   // 4, 3
@@ -364,7 +367,7 @@ static __global__ void __launch_bounds__(WM* WN * 64, OCC * WM* WN / 4) igemm_ha
   // ---- epilogue: igemm.h's (alpha, bias, ReLU, BatchNorm column sums, residual / gates, 16-byte stores), three wave
   //      rows staged per round; no output row map, no stream-K -------------------------------------------------------
   using OT = typename std::conditional<H2, float, half>::type;  // h2: fp32 output and residual, h2 gates (hi halves read)
-  constexpr int OVEC = 16 / (int)sizeof(OT);
+  constexpr int OVEC = EV ? 8 : 16 / (int)sizeof(OT);  // channels a store-pass thread takes from the stage
   OT* out = reinterpret_cast<OT*>(ep.out);
   const OT* res = reinterpret_cast<const OT*>(ep.res);
   const half* gate = reinterpret_cast<const half*>(ep.res_gate);
@@ -386,8 +389,10 @@ static __global__ void __launch_bounds__(WM* WN * 64, OCC * WM* WN / 4) igemm_ha
           for (int r = 0; r < 16; ++r) {
             float v = acc[i][j][r] * ep.alpha + bias;
             if (ep.relu & 1) v = fmaxf(v, 0.f);
-            s1[j] += v;
-            s2[j] += v * v;
+            if constexpr (!EV) {
+              s1[j] += v;
+              s2[j] += v * v;
+            }
             const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
             stage[lr * SC + (lc - nh * SC)] = v;
           }
@@ -411,7 +416,9 @@ static __global__ void __launch_bounds__(WM* WN * 64, OCC * WM* WN / 4) igemm_ha
             v[e + 3] = f[3];
           }
           const long idx = (long)row * ep.ldc + col;
-          if constexpr (H2) {
+          if constexpr (EV) {
+            bn_eval_store8(ep, g.N, row, col, v);
+          } else if constexpr (H2) {
             const long gidx = h2_index(row, ep.ldc, col);
             if (res) {
               PieceView<float> rv;
@@ -465,6 +472,7 @@ static __global__ void __launch_bounds__(WM* WN * 64, OCC * WM* WN / 4) igemm_ha
       }
       __syncthreads();
     }
+  if constexpr (EV) return;
   if (ep.stats || ep.stats_accum) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -590,6 +598,8 @@ inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw,
 // The generic kernel is DMA-bound at the same 330 us (24 KB of LDS-DMA per K-step of 48 MFMAs at ~20 B/clk/CU).)
 // h2 form: `g2` is the doubled geometry launch_igemm_h2 builds (g2.C = 2 x real channels); every 3x3 stride-1 shape the fp16
 // kernels cover, the 256-column shape when it fills the chip in one round (layer3), the 128-column shape otherwise
+// EV: the fused inference epilogue; the same choice for both forms (igemm.h launch_igemm_h2)
+template <bool EV>
 inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream) {
   const int gm = cdiv(g2.M, 288);
   const bool q = g2.mma == MMA_H2Q;  // h2q operands: the scaled-fp8 cross terms (igemm_halo_kernel Q)
@@ -600,7 +610,10 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
   const bool force256 = knobs().h2_halo256;
   const int a1 = knobs().halo_a1;  // (see launch_igemm_halo)
   if (g2.N % 256 == 0 && ((tiles288 > 192 && tiles288 <= device_cus()) || force256) && igemm_halo_applies(g2, ep, 256, 352)) {
-    if (q)
+    if constexpr (EV)
+      hipLaunchKernelGGL((igemm_halo_kernel<256, 352, 0, 1, true, 3, 4, false, 1, false, true>), dim3(gm * (g2.N / 256)), dim3(768), 0, stream, g2, A, Bw, ep,
+                       g2.N / 256, rd);
+    else if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<256, 352, 0, 1, true, 3, 4, false, 1, true>), dim3(gm * (g2.N / 256)), dim3(768), 0, stream, g2, A, Bw, ep,
                        g2.N / 256, rd);
     else
@@ -612,7 +625,10 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
   // (measured: 338 -> 304 us forward, 356 -> 326 data gradient, step 29.69 -> 29.52 ms; 288-row tiles of 6 waves at two workgroups
   //  per CU -- 27 % less DMA per row -- 409 us: six waves do not spread over four SIMDs; profiles/r04/c15_*, c16_*)
   if (g2.N == 64 && igemm_halo_applies(g2, ep, 64, 368, 192)) {
-    if (q)
+    if constexpr (EV)
+      hipLaunchKernelGGL((igemm_halo_kernel<64, 368, 0, 1, true, 2, 2, true, 2, false, true>), dim3(cdiv(g2.M, 192)), dim3(256), 0, stream, g2, A, Bw, ep, 1,
+                       rd);
+    else if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<64, 368, 0, 1, true, 2, 2, true, 2, true>), dim3(cdiv(g2.M, 192)), dim3(256), 0, stream, g2, A, Bw, ep, 1,
                        rd);
     else
@@ -623,7 +639,10 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
   // layer1's two-workgroup shape for the 128-column layers with at least two rounds of 192-row tiles (layer2): see launch_igemm_halo
   if (a1 > 0 && g2.N % 128 == 0 && (a1 == 2 || (long)cdiv(g2.M, 192) * (g2.N / 128) >= 2L * device_cus()) &&
       igemm_halo_applies(g2, ep, 128, 288, 192)) {
-    if (q)
+    if constexpr (EV)
+      hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, true, 2, 2, true, 2, false, true>), dim3(cdiv(g2.M, 192) * (g2.N / 128)), dim3(256), 0, stream,
+                       g2, A, Bw, ep, g2.N / 128, rd);
+    else if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, true, 2, 2, true, 2, true>), dim3(cdiv(g2.M, 192) * (g2.N / 128)), dim3(256), 0, stream,
                        g2, A, Bw, ep, g2.N / 128, rd);
     else
@@ -638,7 +657,10 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
     const int cus = device_cus();
     const double e384 = (double)t384 / ((double)cdiv(t384, cus) * cus), e288 = (double)t288 / ((double)cdiv(t288, cus) * cus);
     if (e384 >= e288 - 0.03) {
-    if (q)
+    if constexpr (EV)
+      hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, true, 4, 2, false, 1, false, true>), dim3(cdiv(g2.M, 384) * (g2.N / 128)), dim3(512), 0, stream, g2,
+                         A, Bw, ep, g2.N / 128, rd);
+    else if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, true, 4, 2, false, 1, true>), dim3(cdiv(g2.M, 384) * (g2.N / 128)), dim3(512), 0, stream, g2,
                          A, Bw, ep, g2.N / 128, rd);
     else
@@ -648,7 +670,10 @@ inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half*
     }
   }
   if (igemm_halo_applies(g2, ep, 128, 384)) {
-    if (q)
+    if constexpr (EV)
+      hipLaunchKernelGGL((igemm_halo_kernel<128, 384, 0, 1, true, 3, 4, false, 1, false, true>), dim3(gm * (g2.N / 128)), dim3(768), 0, stream, g2, A, Bw, ep,
+                       g2.N / 128, rd);
+    else if (q)
       hipLaunchKernelGGL((igemm_halo_kernel<128, 384, 0, 1, true, 3, 4, false, 1, true>), dim3(gm * (g2.N / 128)), dim3(768), 0, stream, g2, A, Bw, ep,
                        g2.N / 128, rd);
     else

@@ -224,6 +224,10 @@ struct PlanBase {
   int64_t in_store_frames = 0;
   unsigned char* in_stage = nullptr;
   int64_t in_stage_bytes = 0;
+  // Fused inference pass (mn_set_eval_fused): a training == 0 forward pass of an h2 plan finishes BatchNorm, residual and ReLU in
+  // the epilogues of its convolutions.  Off: every pass launches exactly what it launched before the switch existed
+  bool eval_fused = false;
+  virtual std::string eval_fused_refusal() const = 0;  // empty: this plan can run the fused pass; else why mn_set_eval_fused fails
   virtual int input_grad(const void* images, const float* cot, float* gx_out, float* sal_out, float* poses_out, hipStream_t s) = 0;
   virtual int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) = 0;
   virtual int forward_loss(const void* images, const float* targets, float* loss_out, float* poses_out,
@@ -456,6 +460,9 @@ struct Plan : PlanBase {
   unsigned char* frozen;
   int* stem_colmap;
   RepackJob* repack_jobs;
+  BnEvalJob* bn_eval_jobs = nullptr;  // every BatchNorm unit of the network: the fused inference pass's coefficient launch
+  int bn_eval_njobs = 0;
+  static constexpr int kBnEvalJobs = 40;  // stem + 16 blocks x 2 + 3 projections = 36
   int repack_njobs = 0, repack_blocks = 0, repack_head_jobs = -1, repack_head_blocks = 0;
   unsigned char* pool_idx;  // winning tap of every max-pool window
   float* wgf_ws = nullptr;  // partial tiles of the fused weight gradient (wgrad_fused.h), shared by its launches (one stream)
@@ -590,6 +597,7 @@ struct Plan : PlanBase {
     jit_mean = (float*)A((size_t)B * 4);
     ig_flag = (float*)A(256);  // (input_grad: behind everything else, as above)
     sal_work = (float*)A((size_t)B * kSalChunks * 2 * 4);
+    bn_eval_jobs = (BnEvalJob*)A(kBnEvalJobs * sizeof(BnEvalJob));  // (3 KB behind everything else, as above)
     return b.cur;
   }
 
@@ -687,6 +695,7 @@ struct Plan : PlanBase {
       }
     }
     build_repack_table(s);
+    build_bn_eval_table(s);
     update_frozen(s);
     weights_dirty = true;
     return check_launch("attach");
@@ -730,6 +739,27 @@ struct Plan : PlanBase {
     repack_njobs = (int)jobs.size();
     repack_blocks = blk;
     hipMemcpyAsync(repack_jobs, jobs.data(), jobs.size() * sizeof(RepackJob), hipMemcpyHostToDevice, s);
+    hipStreamSynchronize(s);  // `jobs` is a host temporary
+  }
+  // the BatchNorm units of the network in pass order (bn_eval_coef_all_kernel, elementwise.h)
+  void build_bn_eval_table(hipStream_t s) {
+    std::vector<BnEvalJob> jobs;
+    auto add = [&](const Unit& u) {
+      BnEvalJob j;
+      j.p = bn_params(u);
+      j.coef = u.coef_f;
+      j.C = u.cp.cout;
+      jobs.push_back(j);
+    };
+    add(stem);
+    for (auto& bk : blocks) {
+      if (bk.down) add(bk.ud);
+      add(bk.u1);
+      add(bk.u2);
+    }
+    bn_eval_njobs = (int)jobs.size();
+    if (bn_eval_njobs > kBnEvalJobs) bn_eval_njobs = 0;  // (cannot happen for this network; mn_set_eval_fused then refuses)
+    hipMemcpyAsync(bn_eval_jobs, jobs.data(), (size_t)bn_eval_njobs * sizeof(BnEvalJob), hipMemcpyHostToDevice, s);
     hipStreamSynchronize(s);  // `jobs` is a host temporary
   }
   // head = stem + layer1 weights (needed first), tail = everything else; the tail can run on the side stream
@@ -804,6 +834,27 @@ struct Plan : PlanBase {
       launch_conv_halo_pp(u.gf, (const half*)x, (const half*)u.wf, ep, s);
     else
       launch_igemm<T>(u.gf, x, u.wf, ep, s, (const T*)zero_page);
+    timer.end(tp, s);
+  }
+  // Fused inference pass: out(h2) = [relu](conv(x; u) * scale + shift [+ res(h2)]) in ONE launch -- the kernel and tile shape
+  // conv_bn_stats picks for this geometry, with the fused epilogue (igemm.h EV); u.y is not written.  u.coef_f holds this pass's
+  // coefficients (bn_eval_coef_all_kernel at the head of the pass).
+  std::string eval_fused_refusal() const override {
+    static const char* const names[] = {"fp32", "fp16", "fp32x3", "fp16x2", "fp16x2m", "fp16x2q"};
+    if (md.act != FMT_H2)
+      return std::string("the fused inference pass needs h2 activations (fp16x2, fp16x2m); this plan computes in ") +
+             (cfg.dtype >= 0 && cfg.dtype < 6 ? names[cfg.dtype] : "an unknown dtype");
+    if (bn_eval_njobs <= 0) return "the coefficient job table does not hold this network's BatchNorm units";
+    return "";
+  }
+  void conv_bn_eval(Unit& u, const T* x, const T* res, int relu, T* out, hipStream_t s) {
+    Epilogue ep = stats_epilogue(u, 0);  // what the dispatcher reads is the unfused launch's
+    ep.out = out;
+    ep.bn_coef = u.coef_f;
+    ep.bn_res = res;
+    ep.bn_relu = relu;
+    auto* tp = timer.begin(0, s);
+    launch_igemm_h2<true>(u.gf, (const half*)x, (const half*)u.wf, ep, s, (const half*)zero_page, false);
     timer.end(tp, s);
   }
   // the stem reads 3 channels (no 32-channel groups, no halo): its own kernels, or the generic implicit GEMM on exact fp32
@@ -904,9 +955,15 @@ struct Plan : PlanBase {
       if (dirty) repack_tail(side);
       if (zero_grads) launch_zero_fill(grads, L.param_floats, side);
     }
+    // the fused inference pass: every unit's (scale, shift), mean and invstd from the running statistics in one launch, here at
+    // the head of the pass -- after an optimiser step or a load_state_dict there is nothing to mark dirty
+    const bool fused = eval_fused && !training;  // (mn_set_eval_fused turns it on only for a plan that can run it)
+    if (fused)
+      hipLaunchKernelGGL(bn_eval_coef_all_kernel, dim3(bn_eval_njobs * kBnEvalChunks), dim3(256), 0, s, (const BnEvalJob*)bn_eval_jobs,
+                         bn_eval_njobs);
     stem_conv(training, s);
     if (md.pairs()) {  // (always the fused form: fp32 conv output in, h2 pooled activation out)
-      bn_finalize(stem, s);
+      if (!fused) bn_finalize(stem, s);
       hipLaunchKernelGGL(bn_relu_maxpool_h2_kernel, dim3(ew_grid((long)B * H1 * W1 * 64 / 8)), dim3(256), 0, s,
                          (const float*)stem.y, (const float*)stem.coef_f, (half*)p0, pool_idx, B, H0, W0, 64, H1, W1,
                          training && md.stem_bwd == STEM_TILES_ON_COPIES ? (half*)a0 : (half*)nullptr, md.act == FMT_H2Q ? 1 : 0);
@@ -921,6 +978,13 @@ struct Plan : PlanBase {
     }
     for (auto& blk : blocks) {
       if (blk.stage >= 1) join_wgrad(s);  // no-op once joined
+      if (fused) {  // three launches per down block, two per other block; the fork and join of the projection path as below
+        if (blk.down) conv_bn_eval(blk.ud, blk.x, nullptr, 0, blk.zd, fork_wgrad(s));
+        conv_bn_eval(blk.u1, blk.x, nullptr, 1, blk.a1, s);
+        if (blk.down) join_wgrad(s);
+        conv_bn_eval(blk.u2, blk.a1, blk.down ? blk.zd : blk.x, 1, blk.out, s);
+        continue;
+      }
       // The projection path of a down block (1x1 stride-2 convolution, BatchNorm) depends on the block's input only: it runs on the
       // side stream -- idle in the forward pass -- beside conv1 -> bn1 -> conv2 and is joined before the residual add.  Three blocks,
       // ~0.25 ms of small launches: fp16x2m 18.18 -> 18.05 ms, four of four interleaved pairs (profiles/r06/c41_c42_*).
@@ -1656,6 +1720,15 @@ extern "C" int mn_set_input_index(mn_handle* h, const int32_t* index_dev, int64_
 extern "C" int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls) {
   MN_H(h);
   P.jit_calls = calls;
+  return 0;
+}
+extern "C" int mn_set_eval_fused(mn_handle* h, int enable) {
+  MN_H(h);
+  if (enable) {
+    const std::string why = P.eval_fused_refusal();
+    if (!why.empty()) return fail("mn_set_eval_fused: " + why);
+  }
+  P.eval_fused = enable != 0;
   return 0;
 }
 extern "C" int mn_forward(mn_handle* h, const void* images, float* poses_out, int training, void* stream) {

@@ -96,6 +96,33 @@ extern "C" int mn_op_igemm(int dtype, const mn_gather_geom* gg, const void* A, c
   return check_launch("igemm");
 }
 
+// The fused inference convolution of mn_set_eval_fused on its own: out(h2) = [relu](conv(A; Bw) * scale + shift [+ res(h2)]).
+// The launch goes through the plan's dispatcher, so the kernel and tile shape are the ones mn_op_igemm(MN_DTYPE_F16X2) takes for
+// the same geometry (and the same MN_* knobs) with stats = bias = res = NULL, relu = 0, alpha = 1.
+extern "C" int mn_op_conv_bn_eval(int dtype, const mn_gather_geom* gg, const void* A, const void* Bw, const float* coef,
+                                  const void* res, int relu, void* out, int ldc, const void* zero_page, void* stream) {
+  begin_op();
+  if (dtype != MN_DTYPE_F16X2 && dtype != MN_DTYPE_F16X2M)
+    return fail("conv_bn_eval: dtype must be MN_DTYPE_F16X2 or MN_DTYPE_F16X2M (h2 operands, residual and output)");
+  if (!gg || !A || !Bw || !out) return fail("conv_bn_eval: geometry, A, Bw and out are required");
+  GatherGeom g = to_geom(gg);
+  if (g.C % 32 != 0) return fail("conv_bn_eval: h2 operands need C % 32 == 0");
+  if (g.N % 8 != 0) return fail("conv_bn_eval: N % 8 == 0 required (a store-pass thread writes 8 channels)");
+  if (int e = check_geom(g, MN_DTYPE_F16X2)) return e;
+  if (!coef) return fail("conv_bn_eval: coef (fp32 [2][N]: scale | shift) is required");
+  if (((uintptr_t)coef & 15) != 0) return fail("conv_bn_eval: coef must be 16-byte aligned");
+  if (ldc < g.N || ldc % 32 != 0) return fail("conv_bn_eval: ldc must be a multiple of 32 (h2 rows) and at least N");
+  if (!zero_page) return fail("conv_bn_eval: zero_page (>= 16 zero bytes of device memory) is required");
+  if ((long)gg->B * gg->Hi * gg->Wi * gg->C * 4 >= 0xfffffff0l || (long)gg->N * gg->K * 4 >= 0xfffffff0l)
+    return fail("conv_bn_eval: operands must be smaller than 4 GiB (32-bit buffer offsets)");
+  Epilogue ep;
+  ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr; ep.res_gate = nullptr;
+  ep.alpha = 1.f;
+  ep.bn_coef = coef; ep.bn_res = res; ep.bn_relu = relu ? 1 : 0;
+  launch_igemm_h2<true>(g, (const half*)A, (const half*)Bw, ep, (hipStream_t)stream, (const half*)zero_page, false);
+  return check_launch("conv_bn_eval");
+}
+
 static int op_conv_halo_pp(const mn_gather_geom* gg, const void* A, const void* Bw, void* out, int ldc, double* stats_accum,
                            int stats_rows, int relu, const void* res, const void* res_gate, const void* out_gate, float alpha, int wgs,
                            bool gate_h2, void* stream) {

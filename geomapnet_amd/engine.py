@@ -113,6 +113,9 @@ class Engine:
         self.jitter_calls = 0
         # the `size` of the device Resize on uint8 input (mn_set_input_resize; data.resize_dims): an int, a pair (H, W), None = off
         self.input_resize = None
+        # the fused inference pass (mn_set_eval_fused): eval-mode forward passes finish BatchNorm, residual and ReLU in the epilogues
+        # of their convolutions; propagated to every plan, existing and future
+        self.eval_fused = False
 
     # -- arenas ---------------------------------------------------------------------------------
     @property
@@ -243,6 +246,9 @@ class Engine:
                                                      C.c_uint64(seed)))
             p["color_jitter"] = self.color_jitter
             p["jitter_calls"] = 0  # (mn_set_color_jitter restarts the plan's count; _jitter_pass continues the model's)
+        if p.get("eval_fused", False) != self.eval_fused:  # (the library refuses plans whose activations are not h2 tensors)
+            self.lib.check(self.lib.set_eval_fused(p["handle"], int(self.eval_fused)))
+            p["eval_fused"] = self.eval_fused
         self._own_step(p)
         return p
 
@@ -373,6 +379,25 @@ class Engine:
         if (len(size) != 2 or min(size) < 1) if isinstance(size, tuple) else size < 1:
             raise MapNetHipError("set_input_resize: size must be a positive int or a pair (H, W) of them")
         self.input_resize = size
+
+    EVAL_FUSED_DTYPES = ("fp16x2", "fp16x2m")
+
+    def set_eval_fused(self, enable=True):
+        """eval-mode forward passes run the fused inference pass (include/mapnet_hip.h mn_set_eval_fused): the same poses bit for
+        bit, two launches per block instead of six and no fp32 conv output through HBM.  Opt-in; training passes and input
+        gradients are untouched.  Plans whose activations are not h2 tensors are refused: the library's error is raised here for
+        the plans that exist, and the same refusal, with the dtype named, when the model's compute dtype has none yet."""
+        enable = bool(enable)
+        if enable:
+            dtype = self.dtype or _default_dtype
+            if dtype not in self.EVAL_FUSED_DTYPES:
+                raise MapNetHipError("mn_set_eval_fused: the fused inference pass needs h2 activations (%s); this model computes in %s "
+                                     "(set_compute_dtype)" % (", ".join(self.EVAL_FUSED_DTYPES), dtype))
+        for p in self.plans.values():
+            if p.get("eval_fused", False) != enable:
+                self.lib.check(self.lib.set_eval_fused(p["handle"], int(enable)))
+                p["eval_fused"] = enable
+        self.eval_fused = enable
 
     def source_dims(self, images):
         """-> (h, w) of the frames as they arrive when the device Resize is on, else None: the `src` of plan()"""

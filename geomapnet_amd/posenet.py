@@ -228,6 +228,12 @@ class PoseNet(_ArenaModule):
         Normalize.  size: int (smaller edge -> size, data.resize_dims) or (H, W); None turns it off."""
         self._engine.set_input_resize(size)
 
+    def set_eval_fused(self, enable=True):
+        """The fused inference pass for eval-mode forward passes (fp16x2 / fp16x2m): every block unit finishes BatchNorm, residual and
+        ReLU in the epilogue of its convolution -- the same poses bit for bit in fewer launches and less HBM traffic.  Off by
+        default; train() passes are untouched.  Raises for a compute dtype whose activations are not h2 tensors."""
+        self._engine.set_eval_fused(enable)
+
     def forward(self, x):
         u8 = self._engine.input_u8 is not None
         if x.dim() != 4 or (x.shape[-1] if u8 else x.shape[1]) != 3:
@@ -298,6 +304,9 @@ class MapNet(nn.Module):
 
     def set_input_resize(self, size=256):
         self.mapnet.set_input_resize(size)
+
+    def set_eval_fused(self, enable=True):
+        self.mapnet.set_eval_fused(enable)
 
     def load_state_dict(self, state_dict, strict=True):
         r = super().load_state_dict(state_dict, strict)

@@ -236,6 +236,21 @@ int mn_set_color_jitter_calls(mn_handle* h, uint32_t calls);
 int64_t mn_input_resize_bytes(const mn_config* cfg, int src_h, int src_w);
 int mn_set_input_resize(mn_handle* h, int src_h, int src_w, void* work, int64_t work_bytes);
 
+/* Fused inference pass (opt-in; a new plan starts with it off).  While on, mn_forward with training == 0 finishes every block
+ * unit in the epilogue of its convolution: BatchNorm from the running statistics is a per-channel (scale, shift) known before the
+ * convolution starts, so the accumulators leave the kernel as the finished h2 activation (+ h2 residual, ReLU) and neither the fp32
+ * conv output nor the separate finalize / apply launches exist: two launches per block (three with a projection) where there were
+ * six (nine).  One launch at the head of the pass computes the coefficients, mean and invstd of ALL BatchNorm units from the
+ * running statistics as they are at that moment: an optimiser step or new buffers (mn_params_changed) in between need no notice.  Every convolution
+ * runs the kernel and tile shape of the unfused pass with the same accumulators, and the per-element arithmetic behind them is the
+ * apply kernel's, so poses and activations ("a1", "out", "zd" of mn_debug_tensor) are the unfused pass's bit for bit; the raw conv
+ * outputs ("y1", "y2", "yd") are NOT written by a fused pass.  Training passes, mn_input_grad and the stem are untouched; the stem
+ * takes its coefficients from the same launch.  Governs mn_forward from the next call on.  Supported for plans whose activations are
+ * h2 tensors (MN_DTYPE_F16X2, MN_DTYPE_F16X2M); enabling it on MN_DTYPE_F32 / _F32X3 / _F16 / _F16X2Q plans fails with the dtype
+ * named (fp16x2q: no fused instantiations of the scaled-fp8 kernels are built).  The work arena grows by a 3 KB job table at its
+ * end for every plan; nothing else in it moves. */
+int mn_set_eval_fused(mn_handle* h, int enable);
+
 /* Batches gathered by index from a device-resident frame store: replaces the batch assembly of the reference's host loader -- the
  * DataLoader + default_collate of common/train.py:180-188 and the torch.stack of MF.__getitem__, dataset_loaders/composite.py:77-83 --
  * for sequences that were uploaded once.  mn_set_input_index: index_dev is device int32 [images] (4-byte aligned); while it is set,
@@ -348,6 +363,16 @@ int mn_op_igemm(int dtype, const mn_gather_geom* g, const void* A, const void* B
                 const float* bias, int relu, const void* res, const void* res_gate, float alpha, const void* zero_page,
                 void* stream);
 int mn_op_igemm_grid_m(int M);
+/* The fused inference convolution of mn_set_eval_fused on its own:
+ *   out[m][n] = [relu]( sum_k gather(A)[m][k] * Bw[n][k] * coef[n] + coef[N + n] [+ res[m][n]] )
+ * dtype MN_DTYPE_F16X2 (or _F16X2M, whose forward kernels are the same); any other dtype fails.  A, Bw, res (or NULL) and out are
+ * h2 tensors (out, res: [M][ldc], ldc % 32 == 0), coef is fp32 [2][N] (scale | shift, 16-byte aligned, required), C % 32 == 0 and
+ * N % 8 == 0.  The arithmetic per element is the BatchNorm apply kernel's in its order (multiply-add, residual, ReLU, split into
+ * fp16 halves).  The launch takes the kernel and tile shape mn_op_igemm(3, ...) takes for the same geometry and MN_* knobs with
+ * stats = bias = res = NULL, relu = 0, alpha = 1 -- the accumulators are that launch's -- so all three forward kernel families
+ * (csrc/halo_h2.h, csrc/igemm_halo.h, csrc/igemm.h) are reachable by shape.  Operands smaller than 4 GiB; zero_page as above. */
+int mn_op_conv_bn_eval(int dtype, const mn_gather_geom* g, const void* A, const void* Bw, const float* coef, const void* res,
+                       int relu, void* out, int ldc, const void* zero_page, void* stream);
 /* dW[n][colmap(k)] += alpha * sum_m dY[m][n] * gather(X)[m][k]  (fp32 atomics into dW) */
 int mn_op_wgrad(int dtype, const mn_gather_geom* g, const void* dY, int ldy, const void* X, float* dW, int ldw,
                 const int32_t* colmap, float alpha, int target_blocks, const void* zero_page, void* stream);

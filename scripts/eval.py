@@ -48,6 +48,9 @@ def build_parser():
                         help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
                              "transform): the dataset yields frames of --height x --width and the network runs at the resized "
                              "size; needs --u8_input")
+    parser.add_argument("--fused_eval", action="store_true",
+                        help="run the fused inference pass (model.set_eval_fused: BatchNorm, residual and ReLU in the epilogues of "
+                             "the convolutions; the same poses bit for bit in fewer launches).  --dtype fp16x2m or fp16x2")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     return parser
@@ -100,6 +103,8 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
         model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
     if args.device_resize is not None:
         model.set_input_resize(args.device_resize)
+    if args.fused_eval:
+        model.set_eval_fused(True)
 
     # load weights
     weights_filename = osp.expanduser(args.weights)

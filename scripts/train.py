@@ -79,6 +79,10 @@ def build_parser():
                              "it by index on the device (geomapnet_amd/resident.py) instead of stacking frames on the host every "
                              "step; the batch order is the host loader's.  Works with or without --u8_input, --device_resize, "
                              "--device_color_jitter; the store must fit the device's free memory")
+    parser.add_argument("--fused_eval", action="store_true",
+                        help="run the validation passes as the fused inference pass (model.set_eval_fused: BatchNorm, residual and "
+                             "ReLU in the epilogues of the convolutions; the same poses bit for bit); training passes are "
+                             "untouched.  --dtype fp16x2m or fp16x2")
     kinds = ("l1", "mse", "smooth_l1", "huber", "quaternion")
     parser.add_argument("--t_loss_fn", choices=kinds, default="l1",
                         help="the training criterion's t_loss_fn (common/criterion.py:34,55,112; the reference's scripts pass "
@@ -180,6 +184,8 @@ def run(args, datasets=None, _binding=None, log=print):
             raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 "
                              "frames arrive normalised)")
         model.set_input_resize(args.device_resize)
+    if args.fused_eval:  # (governs eval-mode forward passes only: the validation half of Trainer.train_val)
+        model.set_eval_fused(True)
     if args.device_color_jitter and color_jitter > 0:
         assert color_jitter <= 1.0
         if not args.u8_input:
