@@ -267,4 +267,14 @@ __device__ __forceinline__ float to_f(T v) {
 // Host-side helpers -------------------------------------------------------------------------
 namespace mn {
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+inline int ew_grid(long work_items) {
+  // grid-stride kernels: at most 16 workgroups per CU.  (Measured and removed, same-box A/Bs of the whole step in
+  // profiles/r02/c25_*: fewer workgroups per CU -- to leave wave slots to the weight gradients running beside the
+  // HBM-bound passes -- and several pieces per thread for the small tensors of layers 3-4: no gain.)
+  constexpr long cap = 256L * 16;
+  long b = (work_items + 255) / 256;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
 }

@@ -355,6 +355,12 @@ static __global__ void __launch_bounds__(256) criterion_kernel(CriterionArgs a) 
     }
   }
 }
+inline void launch_criterion(const CriterionArgs& a, hipStream_t s) {
+  if (a.t_kind == kLossL1 && a.q_kind == kLossL1)  // (the default: the kinds folded at compile time)
+    hipLaunchKernelGGL(criterion_kernel<false>, dim3(1), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(criterion_kernel<true>, dim3(1), dim3(256), 0, s, a);
+}
 
 // standalone relative-pose op: vos[n][i] = calc_vo_logq(poses[n][i], poses[n][i+1]) (+ VJP)
 static __global__ void __launch_bounds__(256) calc_vos_kernel(const float* poses, int N, int T, float* vos, const float* cot,
@@ -374,6 +380,9 @@ static __global__ void __launch_bounds__(256) calc_vos_kernel(const float* poses
   if (dposes)
     for (int i = 0; i < T; ++i)
       for (int c = 0; c < 6; ++c) dposes[((long)n * T + i) * 6 + c] = grad[i][c];
+}
+inline void launch_calc_vos(const float* poses, int N, int T, float* vos, const float* cot, float* dposes, hipStream_t s) {
+  hipLaunchKernelGGL(calc_vos_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, poses, N, T, vos, cot, dposes);
 }
 
 }  // namespace mn

@@ -12,18 +12,7 @@
 
 namespace mn {
 
-constexpr long kBnReduceWgs = 512;  // workgroups of a BatchNorm-backward reduction (launch_bn_bwd explains)
-
-inline int ew_grid(long work_items) {
-  // grid-stride kernels: at most 16 workgroups per CU.  (Measured and removed, same-box A/Bs of the whole step in
-  // profiles/r02/c25_*: fewer workgroups per CU -- to leave wave slots to the weight gradients running beside the
-  // HBM-bound passes -- and several pieces per thread for the small tensors of layers 3-4: no gain.)
-  constexpr long cap = 256L * 16;
-  long b = (work_items + 255) / 256;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+constexpr long kBnReduceWgs = 512;  // workgroups of a BatchNorm-backward reduction (bn_bwd_rows_per_block explains)
 
 // ---- input: NCHW fp32 -> zero-padded NHWC4 (pad 3 top/left, >=3 bottom/right) -------------------
 // out16 (optional, fp16x2m: the stem's fp16 backward kernels read an fp16 image of the input): the same pixels once more as fp16, from
@@ -91,6 +80,17 @@ static __global__ void __launch_bounds__(256) u8nhwc_to_padded_nhwc4_kernel(cons
       *reinterpret_cast<half4*>(out16 + i * 4) = h;
     }
   }
+}
+// both input conversions: uint8 NHWC frames normalised by nm, or fp32 NCHW frames as they are
+template <typename T>
+inline void launch_input_to_padded_nhwc4(const void* images, bool u8, T* out, int B, int H, int W, int Hp, int Wp,
+                                         const InputNorm& nm, half* out16, hipStream_t s) {
+  const dim3 grid(ew_grid((long)B * Hp * Wp));
+  if (u8)
+    hipLaunchKernelGGL((u8nhwc_to_padded_nhwc4_kernel<T>), grid, dim3(256), 0, s, (const unsigned char*)images, out, B, H, W, Hp, Wp,
+                       nm, out16);
+  else
+    hipLaunchKernelGGL((nchw_to_padded_nhwc4_kernel<T>), grid, dim3(256), 0, s, (const float*)images, out, B, H, W, Hp, Wp, out16);
 }
 
 // ---- BatchNorm statistics -------------------------------------------------------------------------
@@ -189,6 +189,9 @@ static __global__ void __launch_bounds__(256) bn_eval_coef_all_kernel(const BnEv
   const int c = (blockIdx.x % kBnEvalChunks) * 256 + threadIdx.x;
   if (c < job.C) bn_write_coef(job.p, c, job.p.running_mean[c], job.p.running_var[c], job.coef, job.C);
 }
+inline void launch_bn_eval_coef_all(const BnEvalJob* jobs, int njobs, hipStream_t s) {
+  hipLaunchKernelGGL(bn_eval_coef_all_kernel, dim3(njobs * kBnEvalChunks), dim3(256), 0, s, jobs, njobs);
+}
 
 static __global__ void __launch_bounds__(256) bn_finalize_fwd_kernel(const double* __restrict__ accum, double count, BnParams p,
                                                                      int training, float* __restrict__ coef, int C,
@@ -219,6 +222,11 @@ static __global__ void __launch_bounds__(256) bn_finalize_fwd_kernel(const doubl
       if (c == 0 && p.num_batches_tracked) *p.num_batches_tracked += 1;
     }
   }
+}
+inline void launch_bn_finalize_fwd(const double* accum, long M, const BnParams& p, int training, float* coef, int C, int accum_rows,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, accum, (double)M, p, training, coef,
+                     C, accum_rows);
 }
 
 // out = [relu]( y * scale[c] + shift[c] [+ res] ), one 16-byte piece per lane.
@@ -264,6 +272,11 @@ static __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restric
     }
     reinterpret_cast<piece_t*>(out)[i] = o.p;
   }
+}
+template <typename T>
+inline void launch_bn_apply(const T* y, const float* coef, const T* res, T* out, long M, int C, int relu, hipStream_t s) {
+  const long np = M * C / ElemTraits<T>::VEC;
+  hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(ew_grid(np)), dim3(256), 0, s, y, coef, res, out, np, C, relu);
 }
 
 // Stem: BatchNorm (finalize as above) + ReLU + max-pool 3x3/2/1 in one pass: the normalised activation is
@@ -336,6 +349,13 @@ static __global__ void __launch_bounds__(256) bn_relu_maxpool_kernel(const T* __
       for (int e = 0; e < VEC; ++e) idx[i * VEC + e] = arg[e];
     }
   }
+}
+template <typename T>
+inline void launch_bn_relu_maxpool(const T* y, const float* coef, T* out, unsigned char* idx, int B, int H, int W, int C,
+                                   hipStream_t s) {
+  const int Po = maxpool_out(H), Qo = maxpool_out(W);
+  hipLaunchKernelGGL((bn_relu_maxpool_kernel<T>), dim3(ew_grid((long)B * Po * Qo * C / ElemTraits<T>::VEC)), dim3(256), 0, s, y, coef,
+                     out, idx, B, H, W, C, Po, Qo);
 }
 
 // one 16-byte piece of the conv output, read as floats
@@ -534,6 +554,12 @@ static __global__ void __launch_bounds__(256) bn_finalize_bwd_kernel(const doubl
     dbeta[c] += (float)(sg * grad_unscale);
   }
 }
+inline void launch_bn_finalize_bwd(const double* accum, long M, const float* gamma, const float* mean, const float* invstd,
+                                   float* dgamma, float* dbeta, float grad_unscale, const float* sg_beta, float* coef, int C,
+                                   int accum_rows, hipStream_t s) {
+  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, accum, (double)M, gamma, mean,
+                     invstd, dgamma, dbeta, grad_unscale, sg_beta, coef, C, accum_rows);
+}
 
 // apply: gy = k1 * (gm - mg - xhat * mgx)
 template <typename T, bool POOL = false>
@@ -642,6 +668,25 @@ static __global__ void __launch_bounds__(256) bn_fwd_stats_kernel(const T* __res
     atomicAdd(accum + C + idx, b);
   }
 }
+template <typename T>
+inline void launch_bn_fwd_stats(const T* y, long M, int C, double* accum, hipStream_t s) {
+  const int rows_per_block = 256;
+  hipLaunchKernelGGL((bn_fwd_stats_kernel<T>), dim3(cdiv(M, rows_per_block)), dim3(256), 0, s, y, M, C, accum, rows_per_block);
+}
+
+// rows per workgroup of a BatchNorm-backward reduction over M rows of C channels, VEC per thread:
+// ~512 workgroups (2 per CU): the reduction is HBM-bound and needs the whole chip, but every workgroup ends with an LDS
+// reduction and 2 x C fp64 atomics -- at 4096 workgroups (round 1) layers 3-4 did ONE loop iteration per workgroup and
+// that epilogue weighed as much as the loads (same-box A/Bs of the whole step: 4096 workgroups 17.77 ms,
+// 1024 17.60, 512 17.42, 256 17.97; round 4: 512 / 768 / 1024 = 13.48 / 13.58 / 13.63 ms in fp16, equal within
+// 0.1 % on the fp16x2 mode's fp32 tensors, profiles/r04/c36_*)
+inline int bn_bwd_rows_per_block(long M, int C, int VEC) {
+  const int rlanes = 256 / (C / VEC);
+  long rows = (M + kBnReduceWgs - 1) / kBnReduceWgs;
+  rows = ((rows + rlanes - 1) / rlanes) * rlanes;
+  if (rows < 4L * rlanes) rows = 4L * rlanes;
+  return (int)rows;
+}
 
 // BatchNorm backward = reduce -> finalize -> apply.  accum: [accum_rows][2][C] doubles, zero on entry (left holding the
 // sums); coef: [4][C] floats of scratch ([3][C] without the self gate).
@@ -657,17 +702,9 @@ inline void launch_bn_bwd(const T* g, const T* gate, const T* y, long M, int C, 
   constexpr int VEC = ElemTraits<T>::VEC;
   const float* sg_gamma = self_gate_beta ? gamma : nullptr;
   if (self_gate_beta) gate = nullptr;
-  // ~512 workgroups (2 per CU): the reduction is HBM-bound and needs the whole chip, but every workgroup ends with an LDS
-  // reduction and 2 x C fp64 atomics -- at 4096 workgroups (round 1) layers 3-4 did ONE loop iteration per workgroup and
-  // that epilogue weighed as much as the loads (same-box A/Bs of the whole step: 4096 workgroups 17.77 ms,
-  // 1024 17.60, 512 17.42, 256 17.97; round 4: 512 / 768 / 1024 = 13.48 / 13.58 / 13.63 ms in fp16, equal within
-  // 0.1 % on the fp16x2 mode's fp32 tensors, profiles/r04/c36_*)
   constexpr long target = kBnReduceWgs;
   const int rlanes = 256 / (C / VEC);
-  long rows = (M + target - 1) / target;
-  rows = ((rows + rlanes - 1) / rlanes) * rlanes;
-  if (rows < 4L * rlanes) rows = 4L * rlanes;
-  int rows_per_block = (int)rows;
+  const int rows_per_block = bn_bwd_rows_per_block(M, C, VEC);
   const int nblk = cdiv(M, rows_per_block);
   // (4 rows per thread per iteration in flight; 8 measured equal: 15.07 vs 14.99 ms per step)
   // rows in flight per thread: 2 for fp16 tensors (111 instead of 122 registers: one more wave fits beside the side stream's
@@ -698,8 +735,7 @@ inline void launch_bn_bwd(const T* g, const T* gate, const T* y, long M, int C, 
   static long calls = 0;
   if (!(C <= skip_c && ++calls > 400))
 #endif
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, (const double*)accum, (double)M, gamma, mean,
-                     invstd, dgamma, dbeta, grad_unscale, self_gate_beta, coef, C, accum_rows);
+  launch_bn_finalize_bwd(accum, M, gamma, mean, invstd, dgamma, dbeta, grad_unscale, self_gate_beta, coef, C, accum_rows, s);
   if (!apply) return;
   long np = M * C / VEC;
   if (pg.idx)
@@ -721,6 +757,10 @@ static __global__ void __launch_bounds__(256) avgpool_fwd_kernel(const T* __rest
   for (int p = 0; p < HW; ++p) s += (float)in[((long)b * HW + p) * C + c];
   out[i] = s / (float)HW;
 }
+template <typename T>
+inline void launch_avgpool_fwd(const T* in, float* out, int B, int HW, int C, hipStream_t s) {
+  hipLaunchKernelGGL((avgpool_fwd_kernel<T>), dim3(cdiv((long)B * C, 256)), dim3(256), 0, s, in, out, B, HW, C);
+}
 
 // g[b][p][c] = gp[b][c] / HW, zeroed where gate[b][p][c] <= 0 (gate = the pooled activation: the ReLU that produced it)
 // gate_h2 (fp16 tensors): the gate is an h2 tensor (common.h) of which the hi halves are read
@@ -736,6 +776,10 @@ static __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const float* __
     if (gate && !((float)gate[gate_h2 ? h2_index(i / C, C, c) : i] > 0.f)) v = 0.f;
     g[i] = (T)v;
   }
+}
+template <typename T>
+inline void launch_avgpool_bwd(const float* gp, T* g, int B, int HW, int C, const T* gate, int gate_h2, hipStream_t s) {
+  hipLaunchKernelGGL((avgpool_bwd_kernel<T>), dim3(ew_grid((long)B * HW * C)), dim3(256), 0, s, gp, g, B, HW, C, gate, gate_h2);
 }
 
 }  // namespace mn

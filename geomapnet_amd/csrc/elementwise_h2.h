@@ -141,6 +141,11 @@ static __global__ void __launch_bounds__(256) bn_apply_h2_kernel(const float* __
     if (rec) *reinterpret_cast<piece_t*>(rec + row * C + cp * VEC) = rc.p;
   }
 }
+inline void launch_bn_apply_h2(const float* y, const float* coef, const half* res, half* out, long M, int C, int relu, int q, half* rec,
+                               const float* mean, const float* invstd, hipStream_t s) {
+  const long ni = M * C / 8;
+  hipLaunchKernelGGL(bn_apply_h2_kernel, dim3(ew_grid(ni)), dim3(256), 0, s, y, coef, res, out, ni, C, relu, q, rec, mean, invstd);
+}
 
 // Stem: BatchNorm + ReLU + max-pool 3x3/2/1 in one pass, fp32 conv output in, h2 pooled activation + argmax bytes out.
 // The comparison is on the fp32 values (the oracle's), so the routing is the reference's.
@@ -219,6 +224,12 @@ static __global__ void __launch_bounds__(256) bn_relu_maxpool_h2_kernel(const fl
       reinterpret_cast<unsigned long long*>(idx)[i] = packed;
     }
   }
+}
+inline void launch_bn_relu_maxpool_h2(const float* y, const float* coef, half* out, unsigned char* idx, int B, int H, int W, int C,
+                                      half* y16, int q, hipStream_t s) {
+  const int Po = maxpool_out(H), Qo = maxpool_out(W);
+  hipLaunchKernelGGL(bn_relu_maxpool_h2_kernel, dim3(ew_grid((long)B * Po * Qo * C / 8)), dim3(256), 0, s, y, coef, out, idx, B, H, W,
+                     C, Po, Qo, y16, q);
 }
 
 // gy(h2) = k1 * (gm - mg - xhat * mgx): bn_bwd_apply_kernel<float> with 8 channels per thread and an h2 store.  The ReLU gate,
@@ -382,17 +393,11 @@ inline void launch_bn_bwd_rec(const half* g, const half* rec, long M, int C, con
                               float* dgamma, float* dbeta, half* gy, double* accum, float* coef, float grad_unscale, hipStream_t s,
                               bool use_gate, int accum_rows) {
   constexpr int VEC = 8;
-  constexpr long target = kBnReduceWgs;
-  const int rlanes = 256 / (C / VEC);
-  long rows = (M + target - 1) / target;
-  rows = ((rows + rlanes - 1) / rlanes) * rlanes;
-  if (rows < 4L * rlanes) rows = 4L * rlanes;
-  const int rows_per_block = (int)rows;
+  const int rows_per_block = bn_bwd_rows_per_block(M, C, VEC);
   const int nblk = cdiv(M, rows_per_block);
   hipLaunchKernelGGL((bn_bwd_reduce_rec_kernel<4>), dim3(nblk), dim3(256), 0, s, g, rec, M, C, accum, rows_per_block, use_gate ? 1 : 0,
                      accum_rows);
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, (const double*)accum, (double)M, gamma, mean,
-                     invstd, dgamma, dbeta, grad_unscale, (const float*)nullptr, coef, C, accum_rows);
+  launch_bn_finalize_bwd(accum, M, gamma, mean, invstd, dgamma, dbeta, grad_unscale, nullptr, coef, C, accum_rows, s);
   const long np = M * C / VEC;
   hipLaunchKernelGGL(bn_bwd_apply_rec_kernel, dim3(ew_grid(np)), dim3(256), 0, s, g, rec, (const float*)coef, gy, np, C, use_gate ? 1 : 0);
 }
@@ -412,6 +417,9 @@ static __global__ void __launch_bounds__(256) widen_f16_kernel(const half* __res
     reinterpret_cast<piece_t*>(out)[2 * i + 1] = b.p;
   }
 }
+inline void launch_widen_f16(const half* in, float* out, long n, hipStream_t s) {  // n: elements, a multiple of 8
+  hipLaunchKernelGGL(widen_f16_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, s, in, out, n / 8);
+}
 
 // global average pool of an h2 activation
 static __global__ void __launch_bounds__(256) avgpool_fwd_h2_kernel(const half* __restrict__ in, float* __restrict__ out, int B,
@@ -430,6 +438,9 @@ static __global__ void __launch_bounds__(256) avgpool_fwd_h2_kernel(const half* 
   }
   out[i] = s / (float)HW;
 }
+inline void launch_avgpool_fwd_h2(const half* in, float* out, int B, int HW, int C, int q, hipStream_t s) {
+  hipLaunchKernelGGL(avgpool_fwd_h2_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, s, in, out, B, HW, C, q);
+}
 
 // g[b][p][c] = gp[b][c] / HW (fp32), zeroed where the pooled h2 activation is <= 0 (its hi half carries the sign)
 static __global__ void __launch_bounds__(256) avgpool_bwd_h2_kernel(const float* __restrict__ gp, float* __restrict__ g, int B,
@@ -444,6 +455,9 @@ static __global__ void __launch_bounds__(256) avgpool_bwd_h2_kernel(const float*
     if (gate && !((float)gate[h2_index(row, C, c)] > 0.f)) v = 0.f;
     g[i] = v;
   }
+}
+inline void launch_avgpool_bwd_h2(const float* gp, float* g, int B, int HW, int C, const half* gate, hipStream_t s) {
+  hipLaunchKernelGGL(avgpool_bwd_h2_kernel, dim3(ew_grid((long)B * HW * C)), dim3(256), 0, s, gp, g, B, HW, C, gate);
 }
 
 }  // namespace mn

@@ -22,6 +22,10 @@ static __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __res
   s = wave_sum(s);
   if (lane == 0) poses[b * 6 + o] = s + ((o < 3) ? bx[o] : bq[o - 3]);
 }
+inline void launch_head_fwd(const float* feat, const float* Wx, const float* bx, const float* Wq, const float* bq, float* poses, int B,
+                            int K, hipStream_t s) {
+  hipLaunchKernelGGL(head_fwd_kernel, dim3(cdiv((long)B * 6 * 64, 256)), dim3(256), 0, s, feat, Wx, bx, Wq, bq, poses, B, K);
+}
 
 __device__ __forceinline__ float nan_to_zero(float v) { return (v != v) ? 0.f : v; }
 
@@ -60,6 +64,10 @@ static __global__ void __launch_bounds__(256) dropout_fwd_kernel(float* __restri
     feat[i] *= m;
   }
 }
+inline void launch_dropout_fwd(float* feat, float* mask, long n, float p, unsigned long long seed, unsigned call, hipStream_t s) {
+  hipLaunchKernelGGL(dropout_fwd_kernel, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, s, feat, mask, n, p, (unsigned)(seed & 0xffffffffu),
+                     (unsigned)(seed >> 32), call);
+}
 
 // dz[b][k] = (feat[b][k] > 0) * ( sum_o dp[b][o] Wx[o][k]  +  filt( sum_o dp[b][3+o] Wq[o][k] ) )
 // (feat is the post-ReLU feature, so the gate is the ReLU derivative of posenet.py:66)
@@ -80,6 +88,11 @@ static __global__ void __launch_bounds__(256) head_bwd_input_kernel(const float*
   // gradient w.r.t. the vector before the dropout is g * mask
   if (dropmask) g *= dropmask[i];
   dz[i] = (feat[i] > 0.f) ? g : 0.f;
+}
+inline void launch_head_bwd_input(const float* dposes, const float* feat, const float* Wx, const float* Wq, float* dz, int B, int K,
+                                  int filter_nans, const float* dropmask, hipStream_t s) {
+  hipLaunchKernelGGL(head_bwd_input_kernel, dim3(cdiv((long)B * K, 256)), dim3(256), 0, s, dposes, feat, Wx, Wq, dz, B, K, filter_nans,
+                     dropmask);
 }
 
 // dW[o][k] += scale * sum_b dp[b][o] feat[b][k] ; db[o] += scale * sum_b dp[b][o]   (o = 0..5)
@@ -118,6 +131,11 @@ static __global__ void __launch_bounds__(256) head_bwd_weight_kernel(const float
     float* dst = is_w ? ((o < 3) ? dWx + (long)o * K + k : dWq + (long)(o - 3) * K + k) : ((o < 3) ? dbx + o : dbq + (o - 3));
     *dst += v;
   }
+}
+inline void launch_head_bwd_weight(const float* dposes, const float* feat, float* dWx, float* dbx, float* dWq, float* dbq, int B, int K,
+                                   float scale, int filter_nans, hipStream_t s) {
+  hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(cdiv(K + 1, 64)), dim3(256), 0, s, dposes, feat, dWx, dbx, dWq, dbq, B, K, scale,
+                     filter_nans);
 }
 
 }  // namespace mn

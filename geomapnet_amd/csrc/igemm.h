@@ -58,6 +58,16 @@ struct GatherGeom {
   // set it from their dtype argument): ignored by the fp16 kernels
   int mma = MMA_NATIVE;
 };
+// the forward gather of a k x k convolution (cin -> cout channels, stride, pad) over B images of Hin x Win pixels
+inline GatherGeom fwd_geom(int B, int Hin, int Win, int cin, int cout, int k, int stride, int pad, int Hout, int Wout) {
+  GatherGeom g;
+  g.B = B; g.Hi = Hin; g.Wi = Win; g.C = cin; g.P = Hout; g.Q = Wout; g.R = k; g.S = k;
+  g.mul_p = stride; g.mul_q = stride; g.rsign = 1; g.ssign = 1; g.off_h = -pad; g.off_w = -pad; g.div = 1;
+  g.M = B * Hout * Wout; g.N = cout; g.K = k * k * cin;
+  return g;
+}
+// a dense layer C[M][N] = A[M][K] * W[N][K]^T as a 1x1 convolution over M one-pixel images
+inline GatherGeom dense_geom(int M, int N, int K) { return fwd_geom(M, 1, 1, K, N, 1, 1, 0, 1, 1); }
 
 // n / d for 0 <= n < 2^31 without the ~35-instruction software division (Granlund-Montgomery round-up
 // multiplier): q = (mulhi(n, mul) + n) >> shift.  The row -> (image, y, x) decomposition of the gather
@@ -76,16 +86,17 @@ inline FastDiv make_fastdiv(int d) {
 __device__ __forceinline__ int fastdiv(int n, FastDiv f) {
   return (int)((__umulhi((unsigned)n, f.mul) + (unsigned)n) >> f.shift);
 }
+// The defaults are the plain launch: no statistics, no bias, no ReLU, no residual, no gates, alpha 1.
 struct Epilogue {
-  void* out;             // [M][ldc], element type T
-  int ldc;
-  float* stats;          // [grid_m][2][N] column partial sums (sum, sum of squares) or null
+  void* out = nullptr;   // [M][ldc], element type T
+  int ldc = 0;
+  float* stats = nullptr;  // [grid_m][2][N] column partial sums (sum, sum of squares) or null
   double* stats_accum = nullptr;  // alternative: [stats_rows][2][N] fp64 accumulators, added to atomically (row =
   int stats_rows = 0;             // tile_m % stats_rows spreads the same-address contention); consumer sums the rows
-  const float* bias;     // [N] or null
-  int relu;              // max(0, .) after bias
-  const void* res;       // residual [M][ldc] of type T or null
-  const void* res_gate;  // if non-null the residual passes only where res_gate[m][n] > 0
+  const float* bias = nullptr;  // [N] or null
+  int relu = 0;          // max(0, .) after bias
+  const void* res = nullptr;  // residual [M][ldc] of type T or null
+  const void* res_gate = nullptr;  // if non-null the residual passes only where res_gate[m][n] > 0
   // if non-null the stored value (after alpha, bias, residual) is zeroed where out_gate[m][n] <= 0: the data gradient
   // of a block's first conv leaves the kernel already multiplied by the ReLU gate of the block BELOW it, so that none
   // of that gradient's three consumers has to read the gating activation again
@@ -98,7 +109,7 @@ struct Epilogue {
   // stored at pixel (2p + om_a, 2q + om_b) of an om_H x om_W image (also applies to res / res_gate / out_gate)
   int om_on = 0, om_P = 0, om_Q = 0, om_H = 0, om_W = 0, om_a = 0, om_b = 0;
   FastDiv om_dq{0, 0}, om_dp{0, 0};
-  float alpha;           // scale applied to the accumulator
+  float alpha = 1.f;     // scale applied to the accumulator
   // Fused inference epilogue (the EV instantiations of the h2 forward kernels only; off by default): the BatchNorm of an eval pass
   // is a per-channel constant known before the convolution starts, so the accumulators leave the kernel as the FINISHED h2
   // activation -- out(h2) = [relu](acc * scale[n] + shift[n] [+ bn_res(h2)]), bn_apply_h2_kernel's arithmetic in its order -- and
@@ -115,6 +126,12 @@ struct Epilogue {
   // store passes of a tile: layer3 data gradients +29 us per launch against 19.9 us of reduction saved, layer2 +36 against
   // 34.9, whole step 14.94 vs 14.63 ms.  profiles/r03/c16_bn_backward_sums_in_dgrad_epilogue.txt.)
 };
+// the fused inference epilogue on top of the plain launch (the defaults above): out(h2) = [relu](acc * scale + shift [+ res(h2)])
+inline Epilogue eval_epilogue(void* out, int ldc, const float* coef, const void* res, int relu) {
+  Epilogue ep;
+  ep.out = out; ep.ldc = ldc; ep.bn_coef = coef; ep.bn_res = res; ep.bn_relu = relu ? 1 : 0;
+  return ep;
+}
 
 struct RowDiv {
   FastDiv q, p;  // divisors GatherGeom.Q and GatherGeom.P

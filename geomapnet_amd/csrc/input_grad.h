@@ -169,6 +169,9 @@ static __global__ void __launch_bounds__(256) input_grad_seed_kernel(const float
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dposes[i] = scale * (cot ? cot[i] : fill);
 }
+inline void launch_input_grad_seed(const float* cot, float* dposes, int n, float fill, float scale, hipStream_t s) {
+  hipLaunchKernelGGL(input_grad_seed_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, cot, dposes, n, fill, scale);
+}
 
 // ---- BatchNorm backward at inference ------------------------------------------------------------------------------------------
 // y_bn = y * scale[c] + shift[c] with scale = gamma / sqrt(running_var + eps) (the first half of a unit's coef_f in eval mode), so

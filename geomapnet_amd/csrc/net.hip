@@ -50,6 +50,9 @@ extern "C" int mn_model_entry(int feat_dim, int idx, mn_entry* out) {
 extern "C" int64_t mn_model_param_floats(int feat_dim) { return layout_for(feat_dim).param_floats; }
 extern "C" int64_t mn_model_buffer_bytes(int feat_dim) { return layout_for(feat_dim).buffer_bytes; }
 
+// images per window: PoseNet 1, MapNet T, the online modes 2 T
+static int frames_per_window(int mode, int T) { return mode == MN_MODE_POSENET ? 1 : (mode == MN_MODE_MAPNET ? T : 2 * T); }
+
 namespace {
 
 struct Bump {
@@ -243,6 +246,7 @@ struct PlanBase {
   // newly seen skip halves the scale, `scale_growth_interval` clean steps double it (0 = never grow).  The host reacts
   // one or two steps late; until then the device keeps skipping, so no non-finite value reaches weights or moments.
   float cur_scale = 1.f;
+  bool scales_loss = false;  // gradients pass through fp16 (Plan: Mode::overflow_guard); other plans keep the scale at 1
   long long* overflow_host = nullptr;  // (only plans that guard against overflow allocate it) pinned: {last step skipped, skipped steps in total, last skipped attempt, last COMPLETED attempt}
   long long skipped_seen = 0;
   long long done_seen = 0;        // last completed attempt the host has accounted for (overflow_host[3])
@@ -601,13 +605,6 @@ struct Plan : PlanBase {
     return b.cur;
   }
 
-  static GatherGeom fwd_geom(int B, int Hin, int Win, const ConvP& c, int Hout, int Wout) {
-    GatherGeom g;
-    g.B = B; g.Hi = Hin; g.Wi = Win; g.C = c.cin; g.P = Hout; g.Q = Wout; g.R = c.k; g.S = c.k;
-    g.mul_p = c.stride; g.mul_q = c.stride; g.rsign = 1; g.ssign = 1; g.off_h = -c.pad; g.off_w = -c.pad; g.div = 1;
-    g.M = B * Hout * Wout; g.N = c.cout; g.K = c.k * c.k * c.cin;
-    return g;
-  }
   void init_unit(Unit& u, const ConvP& c, const BnP& b, int Hin, int Win) {
     u.cp = c;
     u.bp = b;
@@ -616,7 +613,7 @@ struct Plan : PlanBase {
     u.Hout = (Hin + 2 * c.pad - c.k) / c.stride + 1;
     u.Wout = (Win + 2 * c.pad - c.k) / c.stride + 1;
     u.M = (long)B * u.Hout * u.Wout;
-    u.gf = fwd_geom(B, Hin, Win, c, u.Hout, u.Wout);
+    u.gf = fwd_geom(B, Hin, Win, c.cin, c.cout, c.k, c.stride, c.pad, u.Hout, u.Wout);
     u.ldw = c.k * c.k * c.cin;
     u.dg = make_dgrad_geom(B, Hin, Win, c.cin, c.cout, c.k, c.stride, c.pad, u.Hout, u.Wout, VEC);
     u.gf.mma = md.mma_fwd;
@@ -627,8 +624,9 @@ struct Plan : PlanBase {
   Plan(const mn_config& c) : md(mode_of(c.dtype, knobs().deterministic)) {
     cfg = c;
     cur_scale = c.loss_scale;
+    scales_loss = md.overflow_guard;
     L = Layout(c.feat_dim);
-    frames = (c.mode == MN_MODE_POSENET) ? 1 : (c.mode == MN_MODE_MAPNET ? c.T : 2 * c.T);
+    frames = frames_per_window(c.mode, c.T);
     B = c.windows * frames;
     H = c.H;
     W = c.W;
@@ -648,8 +646,8 @@ struct Plan : PlanBase {
     g.mma = md.mma_fwd;
     stem.gf = g;
     stem.ldw = 147;
-    H1 = (H0 + 2 - 3) / 2 + 1;
-    W1 = (W0 + 2 - 3) / 2 + 1;
+    H1 = maxpool_out(H0);
+    W1 = maxpool_out(W0);
     int h = H1, w = W1;
     for (const BlockP& bp : L.blocks) {
       Block blk;
@@ -766,26 +764,13 @@ struct Plan : PlanBase {
   // while the stem and layer1 execute
   void repack_head(hipStream_t s) {
     const bool split = repack_head_jobs > 0;
-    launch_repack(0, split ? repack_head_blocks : repack_blocks, split ? repack_head_jobs : repack_njobs, s);
+    launch_repack<T>(repack_jobs, split ? repack_head_jobs : repack_njobs, params, 0, split ? repack_head_blocks : repack_blocks,
+                     md.wf, md.wd, s);
   }
   void repack_tail(hipStream_t s) {
     const int hb = repack_head_jobs > 0 ? repack_head_blocks : repack_blocks;
-    if (repack_blocks > hb) launch_repack(hb, repack_blocks - hb, repack_njobs, s);
+    if (repack_blocks > hb) launch_repack<T>(repack_jobs, repack_njobs, params, hb, repack_blocks - hb, md.wf, md.wd, s);
     weights_dirty = false;
-  }
-  // workgroups [first_block, first_block + n_blocks) of the job table's first n_jobs jobs; the kernel by the two copies' formats
-  void launch_repack(int first_block, int n_blocks, int n_jobs, hipStream_t s) {
-    void (*kernel)(const RepackJob*, int, const float*, int) = repack_all_kernel<T>;
-    if constexpr (DT == MN_F32) {
-      if (md.wf == FMT_H2Q)  // forward operand h2q, data-gradient operand plain fp16
-        kernel = repack_all_kernel<float, true, true, true>;
-      else if (md.wf == FMT_H2 && md.wd == FMT_F16)  // forward operand h2, data-gradient operand plain fp16
-        kernel = repack_all_kernel<float, true, true>;
-      else if (md.wf == FMT_H2)
-        kernel = repack_all_kernel<float, true>;
-    }
-    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, (const RepackJob*)repack_jobs, n_jobs, (const float*)params,
-                       first_block);
   }
 
   // ---- forward ------------------------------------------------------------------------------------
@@ -802,22 +787,10 @@ struct Plan : PlanBase {
     p.momentum = 0.1f;
     return p;
   }
-  // no statistics, no bias, no ReLU, no residual, no gates, alpha 1: what every launch below starts from
-  static Epilogue plain_epilogue(void* out, int ldc) {
-    Epilogue ep;
-    ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr; ep.res_gate = nullptr;
-    ep.alpha = 1.f;
-    return ep;
-  }
-  // a dense layer C[M][N] = A[M][K] * W[N][K]^T as a 1x1 convolution over M one-pixel images
-  static GatherGeom dense_geom(int M, int N, int K) {
-    GatherGeom g;
-    g.B = M; g.Hi = 1; g.Wi = 1; g.C = K; g.P = 1; g.Q = 1; g.R = 1; g.S = 1; g.mul_p = 1; g.mul_q = 1; g.rsign = 1;
-    g.ssign = 1; g.off_h = 0; g.off_w = 0; g.div = 1; g.M = M; g.N = N; g.K = K;
-    return g;
-  }
   Epilogue stats_epilogue(Unit& u, int training) {  // raw conv output + (training) its column sums for the BatchNorm
-    Epilogue ep = plain_epilogue(u.y, u.cp.cout);
+    Epilogue ep;
+    ep.out = u.y;
+    ep.ldc = u.cp.cout;
     if (training) {
       ep.stats_accum = u.accum_f;
       ep.stats_rows = u.rows_f;
@@ -848,11 +821,7 @@ struct Plan : PlanBase {
     return "";
   }
   void conv_bn_eval(Unit& u, const T* x, const T* res, int relu, T* out, hipStream_t s) {
-    Epilogue ep = stats_epilogue(u, 0);  // what the dispatcher reads is the unfused launch's
-    ep.out = out;
-    ep.bn_coef = u.coef_f;
-    ep.bn_res = res;
-    ep.bn_relu = relu;
+    const Epilogue ep = eval_epilogue(out, u.cp.cout, u.coef_f, res, relu);  // (what the dispatcher reads is the unfused launch's)
     auto* tp = timer.begin(0, s);
     launch_igemm_h2<true>(u.gf, (const half*)x, (const half*)u.wf, ep, s, (const half*)zero_page, false);
     timer.end(tp, s);
@@ -878,21 +847,15 @@ struct Plan : PlanBase {
     static long calls = 0;
     if (u.cp.cout <= skip_c && ++calls > 400) return;
 #endif
-    hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(u.cp.cout, kBnFinalizeChannels)), dim3(256), 0, s, (const double*)u.accum_f, (double)u.M,
-                       bn_params(u), cur_training, u.coef_f, u.cp.cout, u.rows_f);
+    launch_bn_finalize_fwd(u.accum_f, u.M, bn_params(u), cur_training, u.coef_f, u.cp.cout, u.rows_f, s);
   }
   void bn_act(Unit& u, const T* res, int relu, T* out, hipStream_t s) {
-    long np = u.M * u.cp.cout / VEC;
     bn_finalize(u, s);
-    if (md.pairs()) {  // fp32 conv output in, h2 activation out (residual: an h2 activation)
-      const long ni = u.M * u.cp.cout / 8;
-      hipLaunchKernelGGL(bn_apply_h2_kernel, dim3(ew_grid(ni)), dim3(256), 0, s, (const float*)u.y, (const float*)u.coef_f,
-                         (const half*)res, (half*)out, ni, u.cp.cout, relu, md.act == FMT_H2Q ? 1 : 0,
-                         cur_training ? u.rec : (half*)nullptr, (const float*)u.mean, (const float*)u.invstd);
-      return;
-    }
-    hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(ew_grid(np)), dim3(256), 0, s, (const T*)u.y, (const float*)u.coef_f, res, out,
-                       np, u.cp.cout, relu);
+    if (md.pairs())  // fp32 conv output in, h2 activation out (residual: an h2 activation)
+      launch_bn_apply_h2((const float*)u.y, u.coef_f, (const half*)res, (half*)out, u.M, u.cp.cout, relu, md.act == FMT_H2Q ? 1 : 0,
+                         cur_training ? u.rec : (half*)nullptr, u.mean, u.invstd, s);
+    else
+      launch_bn_apply<T>(u.y, u.coef_f, res, out, u.M, u.cp.cout, relu, s);
   }
 
   // ColorJitter + ToTensor + Normalize (jitter.h); every jittered pass advances jit_calls by one
@@ -942,12 +905,8 @@ struct Plan : PlanBase {
     }
     if (input_u8 && jitter_on())
       launch_jitter_input((const unsigned char*)images, x16, s);
-    else if (input_u8)
-      hipLaunchKernelGGL((u8nhwc_to_padded_nhwc4_kernel<T>), dim3(ew_grid((long)B * Hp * Wp)), dim3(256), 0, s,
-                         (const unsigned char*)images, xpad, B, H, W, Hp, Wp, input_norm, x16);
     else
-      hipLaunchKernelGGL((nchw_to_padded_nhwc4_kernel<T>), dim3(ew_grid((long)B * Hp * Wp)), dim3(256), 0, s,
-                         (const float*)images, xpad, B, H, W, Hp, Wp, x16);
+      launch_input_to_padded_nhwc4<T>(images, input_u8, xpad, B, H, W, Hp, Wp, input_norm, x16, s);
     // forked AFTER the (HBM-bound) input conversion, so that the side stream's copies run beside the stem's MFMA-bound
     // convolution instead of competing with the conversion for bandwidth (step time: equal within noise)
     if (dirty || zero_grads) {
@@ -958,23 +917,19 @@ struct Plan : PlanBase {
     // the fused inference pass: every unit's (scale, shift), mean and invstd from the running statistics in one launch, here at
     // the head of the pass -- after an optimiser step or a load_state_dict there is nothing to mark dirty
     const bool fused = eval_fused && !training;  // (mn_set_eval_fused turns it on only for a plan that can run it)
-    if (fused)
-      hipLaunchKernelGGL(bn_eval_coef_all_kernel, dim3(bn_eval_njobs * kBnEvalChunks), dim3(256), 0, s, (const BnEvalJob*)bn_eval_jobs,
-                         bn_eval_njobs);
+    if (fused) launch_bn_eval_coef_all(bn_eval_jobs, bn_eval_njobs, s);
     stem_conv(training, s);
     if (md.pairs()) {  // (always the fused form: fp32 conv output in, h2 pooled activation out)
       if (!fused) bn_finalize(stem, s);
-      hipLaunchKernelGGL(bn_relu_maxpool_h2_kernel, dim3(ew_grid((long)B * H1 * W1 * 64 / 8)), dim3(256), 0, s,
-                         (const float*)stem.y, (const float*)stem.coef_f, (half*)p0, pool_idx, B, H0, W0, 64, H1, W1,
-                         training && md.stem_bwd == STEM_TILES_ON_COPIES ? (half*)a0 : (half*)nullptr, md.act == FMT_H2Q ? 1 : 0);
+      launch_bn_relu_maxpool_h2((const float*)stem.y, stem.coef_f, (half*)p0, pool_idx, B, H0, W0, 64,
+                                training && md.stem_bwd == STEM_TILES_ON_COPIES ? (half*)a0 : (half*)nullptr,
+                                md.act == FMT_H2Q ? 1 : 0, s);
     } else if (fuse_stem) {  // BatchNorm + ReLU + max-pool in one pass; the normalised stem activation is never stored
       bn_finalize(stem, s);
-      hipLaunchKernelGGL((bn_relu_maxpool_kernel<T>), dim3(ew_grid((long)B * H1 * W1 * 64 / VEC)), dim3(256), 0, s,
-                         (const T*)stem.y, (const float*)stem.coef_f, p0, pool_idx, B, H0, W0, 64, H1, W1);
+      launch_bn_relu_maxpool<T>(stem.y, stem.coef_f, p0, pool_idx, B, H0, W0, 64, s);
     } else {
       bn_act(stem, nullptr, 1, a0, s);
-      hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(ew_grid((long)B * H1 * W1 * 64 / VEC)), dim3(256), 0, s,
-                         (const T*)a0, p0, pool_idx, B, H0, W0, 64, H1, W1);
+      launch_maxpool_fwd<T>(a0, p0, pool_idx, B, H0, W0, 64, s);
     }
     for (auto& blk : blocks) {
       if (blk.stage >= 1) join_wgrad(s);  // no-op once joined
@@ -1007,14 +962,14 @@ struct Plan : PlanBase {
     const Block& last = blocks.back();
     int F = cfg.feat_dim;
     if (md.pairs())
-      hipLaunchKernelGGL(avgpool_fwd_h2_kernel, dim3(cdiv((long)B * 512, 256)), dim3(256), 0, s, (const half*)last.out, pooled,
-                         B, Hl * Wl, 512, md.act == FMT_H2Q ? 1 : 0);
+      launch_avgpool_fwd_h2((const half*)last.out, pooled, B, Hl * Wl, 512, md.act == FMT_H2Q ? 1 : 0, s);
     else
-      hipLaunchKernelGGL((avgpool_fwd_kernel<T>), dim3(cdiv((long)B * 512, 256)), dim3(256), 0, s, (const T*)last.out, pooled,
-                         B, Hl * Wl, 512);
+      launch_avgpool_fwd<T>(last.out, pooled, B, Hl * Wl, 512, s);
     // fc 512 -> feat_dim, bias, ReLU (models/posenet.py:46,65-66); dropout is the identity under the
     // reference's pinned torch 0.4.1 (F.dropout default training=False)
-    Epilogue ep = plain_epilogue(feat, F);
+    Epilogue ep;
+    ep.out = feat;
+    ep.ldc = F;
     ep.bias = params + L.fc_b;
     ep.relu = 1;
     DenseArgs da;
@@ -1028,14 +983,10 @@ struct Plan : PlanBase {
     // readings): a fresh Philox mask per training forward pass, kept for the backward pass
     drop_this_step = training && drop_p > 0.f;
     if (drop_this_step) {
-      const long n = (long)B * F;
-      hipLaunchKernelGGL(dropout_fwd_kernel, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, s, feat, dropmask, n, drop_p,
-                         (unsigned)(drop_seed & 0xffffffffu), (unsigned)(drop_seed >> 32), drop_calls);
+      launch_dropout_fwd(feat, dropmask, (long)B * F, drop_p, drop_seed, drop_calls, s);
       drop_calls += 1;
     }
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(cdiv((long)B * 6 * 64, 256)), dim3(256), 0, s, (const float*)feat,
-                       (const float*)(params + L.xyz_w), (const float*)(params + L.xyz_b),
-                       (const float*)(params + L.wpqr_w), (const float*)(params + L.wpqr_b), poses, B, F);
+    launch_head_fwd(feat, params + L.xyz_w, params + L.xyz_b, params + L.wpqr_w, params + L.wpqr_b, poses, B, F, s);
     if (poses_out) hipMemcpyAsync(poses_out, poses, (size_t)B * 6 * 4, hipMemcpyDeviceToDevice, s);
     return check_launch("forward");
   }
@@ -1045,10 +996,7 @@ struct Plan : PlanBase {
     a.mode = cfg.mode; a.N = cfg.windows; a.T = cfg.T; a.pred = pred; a.targ = targ; a.s = params + L.crit; a.loss = loss;
     a.dpred = dpred; a.ds = ds; a.vos_out = nullptr; a.grad_scale = cur_scale;
     a.t_kind = t_kind; a.t_param = t_param; a.q_kind = q_kind; a.q_param = q_param;
-    if (t_kind == kLossL1 && q_kind == kLossL1)  // (the default: the kinds folded at compile time)
-      hipLaunchKernelGGL(criterion_kernel<false>, dim3(1), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL(criterion_kernel<true>, dim3(1), dim3(256), 0, s, a);
+    launch_criterion(a, s);
   }
   int loss_only(const float* pred, const float* targ, float* loss_out, hipStream_t s) override {
     run_criterion(pred, targ, loss_out, nullptr, nullptr, s);
@@ -1108,7 +1056,9 @@ struct Plan : PlanBase {
   }
   // gx = data gradient of u (+ res), zeroed where out_gate <= 0
   void conv_dgrad(Unit& u, T* gx, const T* res, hipStream_t s, const T* out_gate = nullptr) {
-    Epilogue ep = plain_epilogue(gx, u.cp.cin);
+    Epilogue ep;
+    ep.out = gx;
+    ep.ldc = u.cp.cin;
     ep.res = res;
     ep.out_gate = out_gate;
     auto* tp = timer.begin(0, s);
@@ -1190,9 +1140,8 @@ struct Plan : PlanBase {
   void launch_head_wgrads(hipStream_t st) override {
     const int F = cfg.feat_dim;
     const float unscale = 1.f / cur_scale;
-    hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(cdiv(F + 1, 64)), dim3(256), 0, st, (const float*)dposes,
-                       (const float*)feat, grads + L.xyz_w, grads + L.xyz_b, grads + L.wpqr_w, grads + L.wpqr_b, B, F,
-                       unscale, cfg.filter_nans);
+    launch_head_bwd_weight(dposes, feat, grads + L.xyz_w, grads + L.xyz_b, grads + L.wpqr_w, grads + L.wpqr_b, B, F, unscale,
+                           cfg.filter_nans, st);
     // fc backward: weight + bias gradient in one launch of 32 x 32 tiles (dense.h)
     DenseWgradArgs dw;
     dw.dY = dz; dw.X = pooled; dw.dW = grads + L.fc_w; dw.db = grads + L.fc_b; dw.B = B; dw.F = F; dw.Cin = 512; dw.ldy = F;
@@ -1206,22 +1155,22 @@ struct Plan : PlanBase {
     DenseArgs dd;
     dd.A = dz; dd.W = fcT; dd.bias = nullptr; dd.C = dpooled; dd.M = B; dd.N = 512; dd.K = F; dd.lda = F; dd.ldw = F; dd.ldc = 512;
     dd.relu = 0;
+    Epilogue ep;
+    ep.out = dpooled;
+    ep.ldc = 512;
     if (dense_nt_applies(dd))
       launch_dense_nt(dd, s);
     else
-      launch_igemm<float>(dense_geom(B, 512, F), (const float*)dz, (const float*)fcT, plain_epilogue(dpooled, 512), s,
-                          (const float*)zero_page);
+      launch_igemm<float>(dense_geom(B, 512, F), (const float*)dz, (const float*)fcT, ep, s, (const float*)zero_page);
   }
   void head_backward(hipStream_t s) {
-    int F = cfg.feat_dim;
-    float unscale = 1.f / cur_scale;
+    const int F = cfg.feat_dim;
     if (!grads_zeroed) launch_zero_fill(grads, L.param_floats, s);  // optim.learner.zero_grad()
     grads_zeroed = false;
     run_criterion(poses, cur_targets, cur_loss, dposes, grads + L.crit, s);
     post_loss(cur_loss, s);
-    hipLaunchKernelGGL(head_bwd_input_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, s, (const float*)dposes,
-                       (const float*)feat, (const float*)(params + L.xyz_w), (const float*)(params + L.wpqr_w), dz, B, F,
-                       cfg.filter_nans, drop_this_step ? (const float*)dropmask : (const float*)nullptr);
+    launch_head_bwd_input(dposes, feat, params + L.xyz_w, params + L.wpqr_w, dz, B, F, cfg.filter_nans,
+                          drop_this_step ? dropmask : nullptr, s);
     // The head's and the fc layer's WEIGHT gradients feed nothing downstream: with two streams they leave with the first fork of the
     // backward pass (fork_wgrad), off the chain criterion -> heads -> fc -> average pool -> layer4 (-0.02 ms, four of four
     // pairs, profiles/r06/c43_*)
@@ -1232,14 +1181,11 @@ struct Plan : PlanBase {
     fc_dgrad(s);
     Block& last = blocks.back();
     if (md.f16_bwd_on_pairs())  // fp16 gradient out, gate = the hi halves of the last block's h2 output
-      hipLaunchKernelGGL((avgpool_bwd_kernel<half>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s,
-                         (const float*)dpooled, (half*)last.gout, B, Hl * Wl, 512, (const half*)last.out, 1);
+      launch_avgpool_bwd<half>(dpooled, (half*)last.gout, B, Hl * Wl, 512, (const half*)last.out, 1, s);
     else if (md.pairs())
-      hipLaunchKernelGGL(avgpool_bwd_h2_kernel, dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s, (const float*)dpooled,
-                         (float*)last.gout, B, Hl * Wl, 512, (const half*)last.out);
+      launch_avgpool_bwd_h2(dpooled, (float*)last.gout, B, Hl * Wl, 512, (const half*)last.out, s);
     else
-      hipLaunchKernelGGL((avgpool_bwd_kernel<T>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s,
-                         (const float*)dpooled, last.gout, B, Hl * Wl, 512, (const T*)last.out, 0);
+      launch_avgpool_bwd<T>(dpooled, last.gout, B, Hl * Wl, 512, last.out, 0, s);
   }
   void stem_backward(hipStream_t s) {
     float* const gamma = params + stem.bp.gamma;
@@ -1256,9 +1202,8 @@ struct Plan : PlanBase {
       a.alpha = 1.f / cur_scale;
       a.pre_gated = mx ? 1 : 0;
       launch_stem_bn_reduce(a, B, H, W, Wp, s);
-      hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(64 / kBnFinalizeChannels), dim3(256), 0, s, (const double*)stem.accum_b, (double)stem.M,
-                         (const float*)gamma, (const float*)stem.mean, (const float*)stem.invstd, grads + stem.bp.gamma,
-                         grads + stem.bp.beta, 1.f / cur_scale, (const float*)beta, stem.coef_b, 64, stem.rows_b);
+      launch_bn_finalize_bwd(stem.accum_b, stem.M, gamma, stem.mean, stem.invstd, grads + stem.bp.gamma, grads + stem.bp.beta,
+                             1.f / cur_scale, beta, stem.coef_b, 64, stem.rows_b, s);
       auto* tp = timer.begin(1, s);
       launch_stem_wgrad(a, B, H, W, Wp, s);
       timer.end(tp, s);
@@ -1272,13 +1217,11 @@ struct Plan : PlanBase {
       // passes: neither the activation nor its gradient exists in memory
       pg.idx = pool_idx; pg.gout = gp0; pg.H = H0; pg.W = W0; pg.Po = H1; pg.Qo = W1;
       if (md.gx != md.y) {  // layer1.0's data gradient left gp0 in fp16: widened into ga0 (unused by the fused stem) for the fp32 chain
-        const long n1 = (long)B * H1 * W1 * 64;
-        hipLaunchKernelGGL(widen_f16_kernel, dim3(ew_grid(n1 / 8)), dim3(256), 0, s, (const half*)gp0, (float*)ga0, n1 / 8);
+        launch_widen_f16((const half*)gp0, (float*)ga0, (long)B * H1 * W1 * 64, s);
         pg.gout = ga0;
       }
     } else {
-      hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid((long)B * H0 * W0 * 64 / VEC)), dim3(256), 0, s,
-                         (const unsigned char*)pool_idx, (const T*)gp0, ga0, B, H0, W0, 64, H1, W1);
+      launch_maxpool_bwd<T>(pool_idx, gp0, ga0, B, H0, W0, 64, s);
       g = ga0;
     }
     launch_bn_bwd<T>(g, (const T*)nullptr, (const T*)stem.y, stem.M, 64, gamma, stem.mean, stem.invstd, grads + stem.bp.gamma,
@@ -1313,15 +1256,11 @@ struct Plan : PlanBase {
     else if (in_index) images = in_stage;
     const int F = cfg.feat_dim;
     hipMemsetAsync(ig_flag, 0, sizeof(float), s);
-    hipLaunchKernelGGL(input_grad_seed_kernel, dim3(cdiv((long)B * 6, 256)), dim3(256), 0, s, cot, dposes, B * 6, 1.f / (6.f * (float)B),
-                       cur_scale);
-    hipLaunchKernelGGL(head_bwd_input_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, s, (const float*)dposes,
-                       (const float*)feat, (const float*)(params + L.xyz_w), (const float*)(params + L.wpqr_w), dz, B, F,
-                       cfg.filter_nans, (const float*)nullptr);
+    launch_input_grad_seed(cot, dposes, B * 6, 1.f / (6.f * (float)B), cur_scale, s);
+    launch_head_bwd_input(dposes, feat, params + L.xyz_w, params + L.wpqr_w, dz, B, F, cfg.filter_nans, nullptr, s);
     fc_dgrad(s);
     Block& last = blocks.back();
-    hipLaunchKernelGGL((avgpool_bwd_kernel<T>), dim3(ew_grid((long)B * Hl * Wl * 512)), dim3(256), 0, s, (const float*)dpooled,
-                       last.gout, B, Hl * Wl, 512, (const T*)last.out, 0);
+    launch_avgpool_bwd<T>(dpooled, last.gout, B, Hl * Wl, 512, last.out, 0, s);
     for (int i = (int)blocks.size() - 1; i >= 0; --i) {
       Block& blk = blocks[i];
       const T* below = i == 0 ? (const T*)nullptr : blk.x;  // (block_backward: the ReLU that produced this block's input)
@@ -1331,8 +1270,7 @@ struct Plan : PlanBase {
       if (blk.down) bn_eval_bwd(blk.ud, blk.gout, nullptr, false, s);
       block_input_dgrad(blk, below, s);
     }
-    hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid((long)B * H0 * W0 * 64 / VEC)), dim3(256), 0, s,
-                       (const unsigned char*)pool_idx, (const T*)gp0, ga0, B, H0, W0, 64, H1, W1);
+    launch_maxpool_bwd<T>(pool_idx, gp0, ga0, B, H0, W0, 64, s);
     // the fused BatchNorm + ReLU + max-pool pass never stored a0: the stem's gate is recomputed from y and coef_f
     if (fuse_stem)
       bn_eval_bwd(stem, ga0, stem.y, true, s);
@@ -1435,21 +1373,16 @@ struct Plan : PlanBase {
   int optim_step(float grad_mul, hipStream_t s) override {
     // squared gradient norm: for clip_grad_norm, and (fp16) as the overflow detector of this step
     if (max_grad_norm > 0.f || md.overflow_guard) {
-      const int nb = sqnorm_grid(L.model_floats);
-      if (deterministic && nb <= kSqPartials) {
-        hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, s, (const float*)grads, (long)L.model_floats, sqnorm,
-                           sq_partials);
-        hipLaunchKernelGGL(sqnorm_fold_kernel, dim3(1), dim3(256), 0, s, (const double*)sq_partials, nb, sqnorm);
-      } else {
+      // (MN_DETERMINISTIC: per-workgroup partial sums, folded in index order)
+      double* const partials = deterministic && sqnorm_grid(L.model_floats) <= kSqPartials ? sq_partials : nullptr;
+      if (!partials) {
         if (!sqnorm_clean) hipMemsetAsync(sqnorm, 0, sizeof(double), s);  // (a second optimiser step on one forward pass)
         sqnorm_clean = false;
-        hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, s, (const float*)grads, (long)L.model_floats, sqnorm,
-                           (double*)nullptr);
       }
+      launch_grad_sqnorm(grads, L.model_floats, sqnorm, partials, s);
     }
     attempts += 1;
-    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, step_dev, beta1, beta2, bc_dev, (const double*)sqnorm,
-                       md.overflow_guard ? overflow_dev : (long long*)nullptr, (long long)attempts);
+    launch_adam_prep(step_dev, beta1, beta2, bc_dev, sqnorm, md.overflow_guard ? overflow_dev : nullptr, attempts, s);
     AdamArgs a;
     a.p = params; a.g = grads; a.m = m1; a.v = m2; a.n = L.param_floats; a.n_clip = L.model_floats; a.lr = lr; a.wd = wd;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
@@ -1457,7 +1390,7 @@ struct Plan : PlanBase {
     a.grad_mul = grad_mul; a.max_norm = max_grad_norm; a.sqnorm = sqnorm; a.frozen = frozen; a.eps_mode = cfg.eps_mode;
     a.skip = md.overflow_guard ? overflow_dev : nullptr;
     a.method = optim_method; a.nesterov = nesterov;
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(L.param_floats)), dim3(256), 0, s, a);
+    launch_adam(a, s);
     if (md.overflow_guard && overflow_host)
       hipMemcpyAsync(overflow_host, overflow_dev, 4 * sizeof(long long), hipMemcpyDeviceToHost, s);
     return check_launch("optim_step");
@@ -1489,7 +1422,7 @@ static int validate(const mn_config* c) {
   if (c->feat_dim < 64 || c->feat_dim % 64 != 0) return fail("config: feat_dim must be a multiple of 64");
   if (!(c->loss_scale > 0.f)) return fail("config: loss_scale must be positive");
   {  // the largest activation (stem output, NHWC) must stay below the 4 GiB a 32-bit buffer offset spans
-    const long frames = c->mode == MN_MODE_POSENET ? 1 : (c->mode == MN_MODE_MAPNET ? c->T : 2 * c->T);
+    const long frames = frames_per_window(c->mode, c->T);
     const long px = ((c->H - 1) / 2 + 1) * (long)((c->W - 1) / 2 + 1);
     if (c->windows * frames * px * 64 * (c->dtype == MN_DTYPE_F16 ? 2 : 4) >= 0xfffffff0l)
       return fail("config: batch too large (an activation tensor would exceed 4 GiB); split the batch");
@@ -1597,8 +1530,7 @@ extern "C" int64_t mn_stuck_overflow_steps(mn_handle* h) { return (h && h->plan)
 extern "C" int mn_set_loss_scale(mn_handle* h, float scale, int growth_interval) {
   MN_H(h);
   if (!(scale > 0.f)) return fail("mn_set_loss_scale: scale must be positive");
-  if (P.cfg.dtype != MN_DTYPE_F16 && P.cfg.dtype != MN_DTYPE_F16X2 && P.cfg.dtype != MN_DTYPE_F16X2M &&
-      P.cfg.dtype != MN_DTYPE_F16X2Q && scale != 1.f)
+  if (!P.scales_loss && scale != 1.f)
     return fail("mn_set_loss_scale: fp32 plans do not scale the loss");
   P.cur_scale = scale;
   P.scale_set_at = P.attempts;
@@ -1651,9 +1583,7 @@ extern "C" int mn_set_color_jitter(mn_handle* h, float brightness, float contras
   P.jit_calls = 0;
   return 0;
 }
-static int resize_images(const mn_config* c) {
-  return c->windows * (c->mode == MN_MODE_POSENET ? 1 : (c->mode == MN_MODE_MAPNET ? c->T : 2 * c->T));
-}
+static int resize_images(const mn_config* c) { return c->windows * frames_per_window(c->mode, c->T); }
 extern "C" int64_t mn_input_resize_bytes(const mn_config* cfg, int src_h, int src_w) {
   if (validate(cfg)) return -1;
   if (src_h < 1 || src_w < 1) {
@@ -1770,16 +1700,14 @@ extern "C" int mn_grad_bucket_pack_bf16(mn_handle* h, int stage, void* out_bf16,
   MN_H(h);
   if (stage < 0 || stage > 3 || !out_bf16) return fail("mn_grad_bucket_pack_bf16: stage 0..3 and an output buffer are required");
   const long off = P.L.stage_begin[stage], n = P.L.stage_end[stage] - off;
-  hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(grad_transport_grid(n)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)(P.grad_arena() + off), (__bf16*)out_bf16, n);
+  launch_grad_pack_bf16(P.grad_arena() + off, (__bf16*)out_bf16, n, (hipStream_t)stream);
   return check_launch("grad_bucket_pack_bf16");
 }
 extern "C" int mn_grad_bucket_unpack_bf16(mn_handle* h, int stage, const void* in_bf16, void* stream) {
   MN_H(h);
   if (stage < 0 || stage > 3 || !in_bf16) return fail("mn_grad_bucket_unpack_bf16: stage 0..3 and an input buffer are required");
   const long off = P.L.stage_begin[stage], n = P.L.stage_end[stage] - off;
-  hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(grad_transport_grid(n)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)in_bf16,
-                     P.grad_arena() + off, n);
+  launch_grad_unpack_bf16((const __bf16*)in_bf16, P.grad_arena() + off, n, (hipStream_t)stream);
   return check_launch("grad_bucket_unpack_bf16");
 }
 extern "C" int mn_optim_step(mn_handle* h, float grad_mul, void* stream) {

@@ -115,10 +115,7 @@ extern "C" int mn_op_conv_bn_eval(int dtype, const mn_gather_geom* gg, const voi
   if (!zero_page) return fail("conv_bn_eval: zero_page (>= 16 zero bytes of device memory) is required");
   if ((long)gg->B * gg->Hi * gg->Wi * gg->C * 4 >= 0xfffffff0l || (long)gg->N * gg->K * 4 >= 0xfffffff0l)
     return fail("conv_bn_eval: operands must be smaller than 4 GiB (32-bit buffer offsets)");
-  Epilogue ep;
-  ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr; ep.res_gate = nullptr;
-  ep.alpha = 1.f;
-  ep.bn_coef = coef; ep.bn_res = res; ep.bn_relu = relu ? 1 : 0;
+  const Epilogue ep = eval_epilogue(out, ldc, coef, res, relu);
   launch_igemm_h2<true>(g, (const half*)A, (const half*)Bw, ep, (hipStream_t)stream, (const half*)zero_page, false);
   return check_launch("conv_bn_eval");
 }
@@ -130,9 +127,8 @@ static int op_conv_halo_pp(const mn_gather_geom* gg, const void* A, const void* 
   GatherGeom g = to_geom(gg);
   if (int e = check_geom(g, MN_F16)) return e;
   Epilogue ep;
-  ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = relu; ep.res = res; ep.res_gate = res_gate;
-  ep.out_gate = out_gate; ep.alpha = alpha; ep.stats_accum = stats_accum; ep.stats_rows = stats_rows;
-  ep.gate_h2 = gate_h2;
+  ep.out = out; ep.ldc = ldc; ep.relu = relu; ep.res = res; ep.res_gate = res_gate; ep.out_gate = out_gate; ep.alpha = alpha;
+  ep.stats_accum = stats_accum; ep.stats_rows = stats_rows; ep.gate_h2 = gate_h2;
   if (!conv_halo_pp_applies(g, ep))
     return fail("conv_halo_pp: fp16 3x3 stride-1 same-size convolutions of 64 -> 64 channels only (stats_rows > 0 with stats_accum)");
   launch_conv_halo_pp(g, (const half*)A, (const half*)Bw, ep, (hipStream_t)stream, wgs);
@@ -158,8 +154,7 @@ extern "C" int mn_op_conv_halo_h2(const mn_gather_geom* gg, const void* A, const
   GatherGeom g = to_geom(gg);
   if (int e = check_geom(g, MN_DTYPE_F16X2)) return e;
   Epilogue ep;
-  ep.out = out; ep.ldc = ldc; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = nullptr; ep.res_gate = nullptr;
-  ep.out_gate = nullptr; ep.alpha = 1.f; ep.stats_accum = stats_accum; ep.stats_rows = stats_rows;
+  ep.out = out; ep.ldc = ldc; ep.stats_accum = stats_accum; ep.stats_rows = stats_rows;
   if (!conv_halo_h2_applies(g, ep))
     return fail("conv_halo_h2: 3x3 stride-1 same-size forward convolutions of 64 -> 64 channel h2 tensors only (stats_rows > 0 with stats_accum)");
   launch_conv_halo_h2(g, (const half*)A, (const half*)Bw, ep, (hipStream_t)stream);
@@ -242,8 +237,7 @@ extern "C" int mn_op_head_wgrad(const float* dposes, const float* feat, float* d
                                 float scale, int filter_nans, void* stream) {
   begin_op();
   if (B <= 0 || K <= 0) return fail("head_wgrad: empty problem");
-  hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(cdiv(K + 1, 64)), dim3(256), 0, (hipStream_t)stream, dposes, feat, dWx, dbx, dWq,
-                     dbq, B, K, scale, filter_nans);
+  launch_head_bwd_weight(dposes, feat, dWx, dbx, dWq, dbq, B, K, scale, filter_nans, (hipStream_t)stream);
   return check_launch("head_wgrad");
 }
 
@@ -262,8 +256,7 @@ static int op_stem_bwd(const void* y, const unsigned char* idx, const void* gp, 
   a.pre_gated = pre_gated;
   hipMemsetAsync(accum_scratch, 0, 2 * 64 * sizeof(double), s);
   launch_stem_bn_reduce(a, B, H, W, Wp, s);
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(64 / kBnFinalizeChannels), dim3(256), 0, s, (const double*)accum_scratch, (double)((long)B * H0 * W0), gamma,
-                     mean, invstd, dgamma, dbeta, alpha, beta, coef_scratch, 64, 1);
+  launch_bn_finalize_bwd(accum_scratch, (long)B * H0 * W0, gamma, mean, invstd, dgamma, dbeta, alpha, beta, coef_scratch, 64, 1, s);
   launch_stem_wgrad(a, B, H, W, Wp, s);
   return check_launch("stem_bwd");
 }
@@ -285,8 +278,7 @@ extern "C" int mn_op_stem_bwd_pregated(const void* y, const unsigned char* idx, 
 
 extern "C" int mn_op_oihw_to_ohwi(const float* src, float* dst, int O, int I, int H, int W, int to_ohwi, void* stream) {
   begin_op();
-  hipLaunchKernelGGL(oihw_ohwi_kernel, dim3(ew_grid((long)O * I * H * W)), dim3(256), 0, (hipStream_t)stream, src, dst, O,
-                     I, H, W, to_ohwi);
+  launch_oihw_ohwi(src, dst, O, I, H, W, to_ohwi, (hipStream_t)stream);
   return check_launch("oihw_ohwi");
 }
 
@@ -304,10 +296,7 @@ static int op_criterion(int mode, int N, int T, const float* pred, const float* 
   a.mode = mode; a.N = N; a.T = T; a.pred = pred; a.targ = targ; a.s = s; a.loss = loss; a.dpred = dpred; a.ds = ds;
   a.vos_out = vos_out; a.grad_scale = grad_scale;
   a.t_kind = t_kind; a.t_param = t_param; a.q_kind = q_kind; a.q_param = q_param;
-  if (t_kind == kLossL1 && q_kind == kLossL1)
-    hipLaunchKernelGGL(criterion_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(criterion_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  launch_criterion(a, (hipStream_t)stream);
   return check_launch("criterion");
 }
 
@@ -329,8 +318,7 @@ extern "C" int mn_op_calc_vos(const float* poses, int N, int T, float* vos, cons
                               void* stream) {
   begin_op();
   if (T < 2 || T > kMaxT) return fail("calc_vos: T out of range");
-  hipLaunchKernelGGL(calc_vos_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, poses, N, T, vos, cot,
-                     dposes);
+  launch_calc_vos(poses, N, T, vos, cot, dposes, (hipStream_t)stream);
   return check_launch("calc_vos");
 }
 
@@ -352,9 +340,7 @@ extern "C" int mn_op_conv_dgrad(int dtype, int B, int Hin, int Win, int Cin, int
   if (int e = check_geom(d.full, mixed ? MN_F16 : dtype)) return e;
   if (Cin % vec != 0) return fail("conv_dgrad: Cin must be a multiple of the 16-byte piece");
   Epilogue ep;
-  ep.out = gx; ep.ldc = Cin; ep.stats = nullptr; ep.bias = nullptr; ep.relu = 0; ep.res = res; ep.res_gate = res_gate;
-  ep.out_gate = out_gate; ep.alpha = 1.f;
-  ep.gate_h2 = mixed;
+  ep.out = gx; ep.ldc = Cin; ep.res = res; ep.res_gate = res_gate; ep.out_gate = out_gate; ep.gate_h2 = mixed;
   if (dtype == MN_DTYPE_F32X3) {
     d.full.mma = MMA_BF16X3;
     for (int i = 0; i < d.n_pc; ++i) d.pc[i].g.mma = MMA_BF16X3;
@@ -380,7 +366,7 @@ extern "C" int mn_pgo_optimize(const double* poses, const double* vos, double* o
   PgoArgs a;
   a.poses = poses; a.vos = vos; a.out = out; a.status = status; a.W = W; a.N = N; a.fc = fc_vos ? 1 : 0; a.n_iters = n_iters;
   a.w_ax = sqrt(1.0 / sax); a.w_aq = sqrt(1.0 / saq); a.w_rx = sqrt(1.0 / srx); a.w_rq = sqrt(1.0 / srq);
-  hipLaunchKernelGGL(pgo_kernel, dim3(W), dim3(64), 0, (hipStream_t)stream, a);
+  launch_pgo(a, (hipStream_t)stream);
   return check_launch("pgo");
 }
 
@@ -402,7 +388,7 @@ extern "C" int mn_op_optim(int method, int nesterov, float* p, const float* g, f
   if (max_norm > 0.f) {
     if (!sqnorm_scratch) return fail("adam: clipping needs a scratch double");
     hipMemsetAsync(sqnorm_scratch, 0, sizeof(double), s);
-    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(sqnorm_grid(n_clip)), dim3(256), 0, s, g, (long)n_clip, sqnorm_scratch, (double*)nullptr);
+    launch_grad_sqnorm(g, (long)n_clip, sqnorm_scratch, nullptr, s);
   }
   AdamArgs a;
   a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.n_clip = n_clip; a.lr = lr; a.wd = wd; a.beta1 = beta1; a.beta2 = beta2;
@@ -410,7 +396,7 @@ extern "C" int mn_op_optim(int method, int nesterov, float* p, const float* g, f
   a.grad_mul = grad_mul; a.max_norm = max_norm; a.sqnorm = sqnorm_scratch; a.frozen = nullptr; a.eps_mode = eps_mode;
   a.bc_dev = nullptr;
   a.method = method; a.nesterov = nesterov ? 1 : 0; a.first_step = step <= 1 ? 1 : 0;
-  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n)), dim3(256), 0, s, a);
+  launch_adam(a, s);
   return check_launch("optim");
 }
 
@@ -421,14 +407,12 @@ static const float* bn_stats_finalize(const void* y, int64_t M, int C, const flo
                                       float* running_var, float* mean, float* invstd, float eps, float momentum, double* accum,
                                       hipStream_t s) {
   hipMemsetAsync(accum, 0, 2 * C * sizeof(double), s);
-  int rows_per_block = 256;
-  hipLaunchKernelGGL((bn_fwd_stats_kernel<T>), dim3(cdiv(M, rows_per_block)), dim3(256), 0, s, (const T*)y, (long)M, C,
-                     accum, rows_per_block);
+  launch_bn_fwd_stats<T>((const T*)y, (long)M, C, accum, s);
   BnParams p;
   p.gamma = gamma; p.beta = beta; p.running_mean = running_mean; p.running_var = running_var;
   p.num_batches_tracked = nullptr; p.mean = mean; p.invstd = invstd; p.eps = eps; p.momentum = momentum;
   float* coef = reinterpret_cast<float*>(accum + 2 * C);  // [2][C] floats behind the accumulators
-  hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(C, kBnFinalizeChannels)), dim3(256), 0, s, (const double*)accum, (double)M, p, 1, coef, C, 1);
+  launch_bn_finalize_fwd(accum, (long)M, p, 1, coef, C, 1, s);
   return coef;
 }
 
@@ -437,9 +421,7 @@ static int bn_train_fwd_t(const void* y, int64_t M, int C, const float* gamma, c
                           float* running_var, float* mean, float* invstd, const void* res, int relu, void* out, float eps,
                           float momentum, double* accum, hipStream_t s) {
   const float* coef = bn_stats_finalize<T>(y, M, C, gamma, beta, running_mean, running_var, mean, invstd, eps, momentum, accum, s);
-  long np = M * C / ElemTraits<T>::VEC;
-  hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(ew_grid(np)), dim3(256), 0, s, (const T*)y, coef, (const T*)res,
-                     (T*)out, np, C, relu);
+  launch_bn_apply<T>((const T*)y, coef, (const T*)res, (T*)out, (long)M, C, relu, s);
   return check_launch("bn_train_fwd");
 }
 
@@ -483,9 +465,7 @@ extern "C" int mn_op_bn_train_fwd_h2(const float* y, int64_t M, int C, const flo
   hipStream_t s = (hipStream_t)stream;
   const float* coef = bn_stats_finalize<float>(y, M, C, gamma, beta, running_mean, running_var, mean, invstd, eps, momentum,
                                                accum_scratch, s);
-  const long ni = M * C / 8;
-  hipLaunchKernelGGL(bn_apply_h2_kernel, dim3(ew_grid(ni)), dim3(256), 0, s, y, coef, (const half*)res, (half*)out, ni, C, relu, 0,
-                     (half*)rec, (const float*)mean, (const float*)invstd);
+  launch_bn_apply_h2(y, coef, (const half*)res, (half*)out, (long)M, C, relu, 0, (half*)rec, mean, invstd, s);
   return check_launch("bn_train_fwd_h2");
 }
 
@@ -546,17 +526,14 @@ extern "C" int mn_op_bn_relu_maxpool_h2(const float* y, const float* coef, void*
   begin_op();
   if (int e = check_bn_channels_h2(C)) return e;
   if (B < 1 || H < 1 || W < 1 || !y || !coef || !out) return fail("bn_relu_maxpool_h2: B, H, W >= 1, y, coef and out required");
-  const int Po = (H + 2 - 3) / 2 + 1, Qo = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(bn_relu_maxpool_h2_kernel, dim3(ew_grid((long)B * Po * Qo * C / 8)), dim3(256), 0, (hipStream_t)stream, y, coef,
-                     (half*)out, idx, B, H, W, C, Po, Qo, (half*)y16, 0);
+  launch_bn_relu_maxpool_h2(y, coef, (half*)out, idx, B, H, W, C, (half*)y16, 0, (hipStream_t)stream);
   return check_launch("bn_relu_maxpool_h2");
 }
 
 extern "C" int mn_op_avgpool_fwd_h2(const void* in, float* out, int B, int HW, int C, void* stream) {
   begin_op();
   if (B < 1 || HW < 1 || C < 32 || C % 32 != 0 || !in || !out) return fail("avgpool_fwd_h2: B, HW >= 1, C a multiple of 32, in and out required");
-  hipLaunchKernelGGL(avgpool_fwd_h2_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, (hipStream_t)stream, (const half*)in, out, B, HW,
-                     C, 0);
+  launch_avgpool_fwd_h2((const half*)in, out, B, HW, C, 0, (hipStream_t)stream);
   return check_launch("avgpool_fwd_h2");
 }
 
@@ -565,44 +542,37 @@ extern "C" int mn_op_avgpool_bwd(int dtype, const float* gp, void* g, const void
   if (dtype != MN_DTYPE_F16X2 && dtype != MN_DTYPE_F16X2M)
     return fail("avgpool_bwd: dtype must be MN_DTYPE_F16X2 (fp32 gradient) or MN_DTYPE_F16X2M (fp16 gradient); the gate is an h2 tensor");
   if (B < 1 || HW < 1 || C < 32 || C % 32 != 0 || !gp || !g) return fail("avgpool_bwd: B, HW >= 1, C a multiple of 32, gp and g required");
-  const dim3 grid(ew_grid((long)B * HW * C));
   if (dtype == MN_DTYPE_F16X2M)
-    hipLaunchKernelGGL((avgpool_bwd_kernel<half>), grid, dim3(256), 0, (hipStream_t)stream, gp, (half*)g, B, HW, C, (const half*)gate, 1);
+    launch_avgpool_bwd<half>(gp, (half*)g, B, HW, C, (const half*)gate, 1, (hipStream_t)stream);
   else
-    hipLaunchKernelGGL(avgpool_bwd_h2_kernel, grid, dim3(256), 0, (hipStream_t)stream, gp, (float*)g, B, HW, C, (const half*)gate);
+    launch_avgpool_bwd_h2(gp, (float*)g, B, HW, C, (const half*)gate, (hipStream_t)stream);
   return check_launch("avgpool_bwd");
 }
 
 extern "C" int mn_op_widen_f16(const void* in, float* out, int64_t n, void* stream) {
   begin_op();
   if (n < 8 || n % 8 != 0 || !in || !out) return fail("widen_f16: n a positive multiple of 8, in and out required");
-  hipLaunchKernelGGL(widen_f16_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const half*)in, out, (long)(n / 8));
+  launch_widen_f16((const half*)in, out, (long)n, (hipStream_t)stream);
   return check_launch("widen_f16");
 }
 
 extern "C" int mn_op_maxpool_fwd(int dtype, const void* in, void* out, unsigned char* idx, int B, int H, int W, int C,
                                  void* stream) {
   begin_op();
-  int Po = (H + 2 - 3) / 2 + 1, Qo = (W + 2 - 3) / 2 + 1;
   if (dtype == MN_F16)
-    hipLaunchKernelGGL((maxpool_fwd_kernel<half>), dim3(ew_grid((long)B * Po * Qo * C / 8)), dim3(256), 0,
-                       (hipStream_t)stream, (const half*)in, (half*)out, idx, B, H, W, C, Po, Qo);
+    launch_maxpool_fwd<half>((const half*)in, (half*)out, idx, B, H, W, C, (hipStream_t)stream);
   else
-    hipLaunchKernelGGL((maxpool_fwd_kernel<float>), dim3(ew_grid((long)B * Po * Qo * C / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const float*)in, (float*)out, idx, B, H, W, C, Po, Qo);
+    launch_maxpool_fwd<float>((const float*)in, (float*)out, idx, B, H, W, C, (hipStream_t)stream);
   return check_launch("maxpool_fwd");
 }
 
 extern "C" int mn_op_maxpool_bwd(int dtype, const unsigned char* idx, const void* gout, void* gin, int B, int H, int W,
                                  int C, void* stream) {
   begin_op();
-  int Po = (H + 2 - 3) / 2 + 1, Qo = (W + 2 - 3) / 2 + 1;
   if (dtype == MN_F16)
-    hipLaunchKernelGGL((maxpool_bwd_kernel<half>), dim3(ew_grid((long)B * H * W * C / 8)), dim3(256), 0,
-                       (hipStream_t)stream, idx, (const half*)gout, (half*)gin, B, H, W, C, Po, Qo);
+    launch_maxpool_bwd<half>(idx, (const half*)gout, (half*)gin, B, H, W, C, (hipStream_t)stream);
   else
-    hipLaunchKernelGGL((maxpool_bwd_kernel<float>), dim3(ew_grid((long)B * H * W * C / 4)), dim3(256), 0,
-                       (hipStream_t)stream, idx, (const float*)gout, (float*)gin, B, H, W, C, Po, Qo);
+    launch_maxpool_bwd<float>(idx, (const float*)gout, (float*)gin, B, H, W, C, (hipStream_t)stream);
   return check_launch("maxpool_bwd");
 }
 

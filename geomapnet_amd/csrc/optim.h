@@ -3,6 +3,7 @@
 // /root/reference/common/optimizer.py:21-23, common/train.py:357-359), and the repack of the
 // fp32 master weights into the compute layouts the matrix-core kernels read.
 #pragma once
+#include "../../include/mapnet_hip.h"
 #include "common.h"
 
 namespace mn {
@@ -55,6 +56,12 @@ static __global__ void __launch_bounds__(256) sqnorm_fold_kernel(const double* _
     *accum = v;
   }
 }
+// *accum = (or += without partials: the caller zeroes it) the squared norm of g[0, n); partials: sqnorm_grid(n) doubles or null
+inline void launch_grad_sqnorm(const float* g, long n, double* accum, double* partials, hipStream_t s) {
+  const int nb = sqnorm_grid(n);
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, s, g, n, accum, partials);
+  if (partials) hipLaunchKernelGGL(sqnorm_fold_kernel, dim3(1), dim3(256), 0, s, (const double*)partials, nb, accum);
+}
 
 // optim.learner.zero_grad(): 16-byte stores over the gradient arena (hipMemsetAsync's fill kernel took ~240 us for the
 // 89 MB arena, 0.37 TB/s; this one runs at the store bandwidth)
@@ -85,6 +92,12 @@ static __global__ void __launch_bounds__(256) grad_unpack_bf16_kernel(const __bf
 inline int grad_transport_grid(long n) {
   long b = (n + 255) / 256;
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+inline void launch_grad_pack_bf16(const float* g, __bf16* out, long n, hipStream_t s) {
+  hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(grad_transport_grid(n)), dim3(256), 0, s, g, out, n);
+}
+inline void launch_grad_unpack_bf16(const __bf16* in, float* g, long n, hipStream_t s) {
+  hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(grad_transport_grid(n)), dim3(256), 0, s, in, g, n);
 }
 
 struct AdamArgs {
@@ -142,6 +155,10 @@ static __global__ void adam_prep_kernel(long long* step, float beta1, float beta
     bc[2] = t == 1 ? 1.f : 0.f;  // first step (SGD's momentum buffer)
   }
 }
+inline void launch_adam_prep(long long* step, float beta1, float beta2, float* bc, const double* sqnorm, long long* overflow,
+                             long long attempt, hipStream_t s) {
+  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, step, beta1, beta2, bc, sqnorm, overflow, attempt);
+}
 
 static __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a) {
   if (a.skip && *a.skip) return;  // overflowed step: parameters, moments and step counter stay as they are
@@ -195,6 +212,9 @@ static __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a) {
       upd = (a.lr * sq2 / bc1) * (m / (sqrtf(v) + a.eps));
     a.p[i] = p - upd;
   }
+}
+inline void launch_adam(const AdamArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(a.n)), dim3(256), 0, s, a);
 }
 
 // dst[perm(o,r,s,i)] = (T) src[o][r][s][i]   src is the fp32 master in OHWI
@@ -362,6 +382,23 @@ static __global__ void __launch_bounds__(256) repack_all_kernel(const RepackJob*
   }
 }
 
+// workgroups [first_block, first_block + n_blocks) of the job table's first n_jobs jobs; the kernel by the formats (MN_DTYPE_*
+// codes) of the forward and the data-gradient copies
+template <typename T>
+inline void launch_repack(const RepackJob* jobs, int n_jobs, const float* params, int first_block, int n_blocks, int wf_format,
+                          int wd_format, hipStream_t s) {
+  void (*kernel)(const RepackJob*, int, const float*, int) = repack_all_kernel<T>;
+  if constexpr (ElemTraits<T>::DTYPE == MN_F32) {
+    if (wf_format == MN_DTYPE_F16X2Q)  // forward operand h2q, data-gradient operand plain fp16
+      kernel = repack_all_kernel<float, true, true, true>;
+    else if (wf_format == MN_DTYPE_F16X2 && wd_format == MN_DTYPE_F16)  // forward operand h2, data-gradient operand plain fp16
+      kernel = repack_all_kernel<float, true, true>;
+    else if (wf_format == MN_DTYPE_F16X2)
+      kernel = repack_all_kernel<float, true>;
+  }
+  hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, jobs, n_jobs, params, first_block);
+}
+
 // [rows][cols] fp32 -> [cols][rows] fp32 (fc weight for its data-gradient GEMM)
 static __global__ void __launch_bounds__(256) transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows,
                                                          int cols) {
@@ -391,6 +428,9 @@ static __global__ void __launch_bounds__(256) oihw_ohwi_kernel(const float* __re
     else
       dst[oihw] = src[idx];
   }
+}
+inline void launch_oihw_ohwi(const float* src, float* dst, int O, int I, int H, int W, int to_ohwi, hipStream_t s) {
+  hipLaunchKernelGGL(oihw_ohwi_kernel, dim3(ew_grid((long)O * I * H * W)), dim3(256), 0, s, src, dst, O, I, H, W, to_ohwi);
 }
 
 }  // namespace mn

@@ -269,5 +269,8 @@ static __global__ void __launch_bounds__(64) pgo_kernel(PgoArgs a) {
   for (int i = t; i < 7 * N; i += 64) a.out[(long)w * 7 * N + i] = z[i];
   if (t == 0) a.status[w] = bad;
 }
+inline void launch_pgo(const PgoArgs& a, hipStream_t s) {  // one 64-thread workgroup per window
+  hipLaunchKernelGGL(pgo_kernel, dim3(a.W), dim3(64), 0, s, a);
+}
 
 }  // namespace mn

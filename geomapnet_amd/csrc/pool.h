@@ -8,6 +8,8 @@
 
 namespace mn {
 
+inline int maxpool_out(int n) { return (n + 2 - 3) / 2 + 1; }  // pooled rows / columns of n input rows / columns
+
 template <typename T>
 static __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* __restrict__ in, T* __restrict__ out,
                                                                   unsigned char* __restrict__ idx, int B, int H, int W,
@@ -59,6 +61,12 @@ static __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* __rest
     }
   }
 }
+template <typename T>
+inline void launch_maxpool_fwd(const T* in, T* out, unsigned char* idx, int B, int H, int W, int C, hipStream_t s) {
+  const int Po = maxpool_out(H), Qo = maxpool_out(W);
+  hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(ew_grid((long)B * Po * Qo * C / ElemTraits<T>::VEC)), dim3(256), 0, s, in, out, idx,
+                     B, H, W, C, Po, Qo);
+}
 
 template <typename T>
 static __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const unsigned char* __restrict__ idx,
@@ -103,6 +111,11 @@ static __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const unsigned 
     for (int e = 0; e < VEC; ++e) ov.e[e] = (T)acc[e];
     reinterpret_cast<piece_t*>(gin)[i] = ov.p;
   }
+}
+template <typename T>
+inline void launch_maxpool_bwd(const unsigned char* idx, const T* gout, T* gin, int B, int H, int W, int C, hipStream_t s) {
+  hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid((long)B * H * W * C / ElemTraits<T>::VEC)), dim3(256), 0, s, idx, gout, gin,
+                     B, H, W, C, maxpool_out(H), maxpool_out(W));
 }
 
 // Gradient of one input position of the max-pool, gathered on the fly: sum of the output gradients of the (at
