@@ -109,6 +109,7 @@ _PROTOS = {
     "mn_op_calc_vos": (c_i, [c_void, c_i, c_i, c_void, c_void, c_void, c_void]),
     "mn_pgo_optimize": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
                               C.c_double, c_i, c_void]),
+    "mn_seq_windows": (c_i, [c_void, c_void, c_void, c_i, c_i, c_i, c_i, c_void, c_void, c_void, c_void]),
     "mn_op_adam": (c_i, [c_void, c_void, c_void, c_void, c_i64, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_f, c_f, c_void,
                          c_i, c_void]),
     "mn_op_optim": (c_i, [c_i, c_i, c_void, c_void, c_void, c_void, c_i64, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_f, c_f, c_void,

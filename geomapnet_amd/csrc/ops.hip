@@ -20,6 +20,7 @@
 #include "pool.h"
 #include "rehearsal.h"
 #include "resize.h"
+#include "seq_eval.h"
 #include "stem.h"
 #include "stem_bwd.h"
 #include "wgrad.h"
@@ -368,6 +369,19 @@ extern "C" int mn_pgo_optimize(const double* poses, const double* vos, double* o
   a.w_ax = sqrt(1.0 / sax); a.w_aq = sqrt(1.0 / saq); a.w_rx = sqrt(1.0 / srx); a.w_rq = sqrt(1.0 / srq);
   launch_pgo(a, (hipStream_t)stream);
   return check_launch("pgo");
+}
+
+extern "C" int mn_seq_windows(const float* pose_table, const float* vo_table, const int32_t* win, int L, int W, int N, int fc_vos,
+                              double* poses7, double* vos7, float* bad_flag, void* stream) {
+  begin_op();
+  SeqWinArgs a;
+  a.pose_table = pose_table; a.vo_table = vo_table; a.win = win; a.L = L; a.W = W; a.N = N; a.fc = fc_vos ? 1 : 0;
+  a.poses7 = poses7; a.vos7 = vos7; a.bad = bad_flag;
+  const std::string err = seq_windows_error(a);
+  if (!err.empty()) return fail("mn_seq_windows: " + err);
+  if (bad_flag) hipMemsetAsync(bad_flag, 0, sizeof(float), (hipStream_t)stream);
+  launch_seq_windows(a, (hipStream_t)stream);
+  return check_launch("seq_windows");
 }
 
 extern "C" int mn_op_optim(int method, int nesterov, float* p, const float* g, float* m, float* v, int64_t n, int64_t n_clip,

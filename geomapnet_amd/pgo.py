@@ -33,20 +33,37 @@ def optimize_windows(pred_poses, vos, fc_vos=False, sax=1, saq=1, srx=1, srq=1, 
     if v.ndim != 3 or v.shape[0] != W or v.shape[2] != 7 or v.shape[1] < P:
         raise ValueError("vos must be [W,%d,7] for %d poses per window (fc_vos=%s)" % (P, N, bool(fc_vos)))
     v = np.ascontiguousarray(v[:, :P])  # the chain graph reads only its first N-1 rows (as the reference does)
-    lib = _lib(binding)
     dev = torch.device(device)
-    d_pred = torch.from_numpy(pred).to(dev)
-    d_vos = torch.from_numpy(v).to(dev)
+    d_out = optimize_windows_dev(torch.from_numpy(pred).to(dev), torch.from_numpy(v).to(dev), fc_vos, sax, saq, srx, srq, n_iters,
+                                 binding)
+    return d_out.cpu().numpy()
+
+
+def optimize_windows_dev(d_pred, d_vos, fc_vos=False, sax=1, saq=1, srx=1, srq=1, n_iters=10, binding=None):
+    """`optimize_windows` on tensors that already sit on the device (evaluate.evaluate_sequence assembles them there,
+    mn_seq_windows): d_pred [W,N,7], d_vos [W,P,7] with exactly the graph's P rows, fp64, contiguous, on one device -> the optimised
+    poses [W,N,7] as a tensor on that device.  One mn_pgo_optimize launch on the current stream; the status is read back (the
+    call's one synchronisation) and numpy.linalg.LinAlgError raised as `optimize_windows` does."""
+    if d_pred.dtype != torch.float64 or d_vos.dtype != torch.float64 or d_pred.device != d_vos.device:
+        raise ValueError("optimize_windows_dev: fp64 tensors on one device")
+    if d_pred.dim() != 3 or d_pred.shape[2] != 7 or not d_pred.is_contiguous() or not d_vos.is_contiguous():
+        raise ValueError("optimize_windows_dev: d_pred must be a contiguous [W,N,7]")
+    W, N = d_pred.shape[0], d_pred.shape[1]
+    P = N * (N - 1) // 2 if fc_vos else N - 1
+    if tuple(d_vos.shape) != (W, P, 7):
+        raise ValueError("optimize_windows_dev: d_vos must be [%d,%d,7] for %d poses per window (fc_vos=%s)" % (W, P, N, bool(fc_vos)))
+    lib = _lib(binding)
+    dev = d_pred.device
     d_out = torch.empty_like(d_pred)
     d_status = torch.empty(W, dtype=torch.int32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream) if dev.type == "cuda" else None
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
     lib.check(lib.pgo_optimize(_binding.ptr(d_pred), _binding.ptr(d_vos), _binding.ptr(d_out), _binding.ptr(d_status), W, N,
                                1 if fc_vos else 0, float(sax), float(saq), float(srx), float(srq), int(n_iters), stream))
     status = d_status.cpu().numpy()
     if status.any():
         raise np.linalg.LinAlgError("pose graph: normal matrix not positive definite in window(s) %s"
                                     % np.flatnonzero(status)[:8].tolist())
-    return d_out.cpu().numpy()
+    return d_out
 
 
 class PoseGraph:

@@ -477,6 +477,21 @@ int mn_op_calc_vos(const float* poses, int N, int T, float* vos, const float* co
 int mn_pgo_optimize(const double* poses, const double* vos, double* out, int32_t* status, int W, int N, int fc_vos,
                     double sax, double saq, double srx, double srq, int n_iters, void* stream);
 
+/* The windows of a whole sequence assembled from one pose per frame, in one launch (csrc/seq_eval.h).  Replaces the per-window
+ * host work of the inference loop: the qexp of every window's predictions and VO targets (to_pose7, scripts/eval.py:166-182) and
+ * the vo_func call inside MF.__getitem__ (dataset_loaders/composite.py:88; calc_vos_safe / calc_vos_safe_fc).  In eval mode the
+ * prediction for slot k of window w is the pose of frame win[w][k] whichever window asks, so with pose_table [L][6] (predicted
+ * (t, log q), device fp32), vo_table [L][6] (the poses the VOs are taken from; or NULL) and win [W][N] (device int32):
+ *   poses7 [W][N][7] = (t, qexp(log q)) of pose_table[win[w][k]], fp64 from the fp32 row -- what mn_pgo_optimize reads;
+ *   vos7   [W][P][7] = the same of the fp32 VO six-vector of vo_table[win[w][i]] and vo_table[win[w][j]], computed in fp32 in the
+ *                      host function's operation order without contraction; P = N-1 (consecutive pairs) or N(N-1)/2 (fc_vos:
+ *                      all pairs i<j in lexicographic order).  NULL if and only if vo_table is NULL.  A pair whose two slots hold
+ *                      the same frame (windows clamped at the ends of a sequence) gives exactly (0,0,0,1,0,0,0).
+ * 2 <= N <= 12, W >= 1, L >= 1.  bad_flag (device float, may be NULL) is cleared ahead of the kernel and set to 1 if an index lies
+ * outside [0, L): that slot reads row 0. */
+int mn_seq_windows(const float* pose_table, const float* vo_table, const int32_t* win, int L, int W, int N, int fc_vos,
+                   double* poses7, double* vos7, float* bad_flag, void* stream);
+
 /* fused Adam over a flat range; replaces torch.optim.Adam.step + clip_grad_norm */
 int mn_op_adam(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_clip, float lr, float wd,
                float beta1, float beta2, float eps, int64_t step, float grad_mul, float max_norm, double* sqnorm_scratch,

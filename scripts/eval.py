@@ -6,7 +6,8 @@ Command line of the reference's scripts/eval.py (/root/reference/scripts/eval.py
 `model_state_dict` through the prefix-aware `load_state_dict`, run windows of `steps` frames with batch size 1,
 keep the middle prediction, optionally optimise every window's pose graph (`--pose_graph`, one batched HIP
 launch over all windows), un-normalise, report median / mean translation and rotation error
-(eval.py:153-205).  Additions: `--dataset Synthetic` (+ `--synthetic_length --height --width`), `--dtype`;
+(eval.py:153-205).  Additions: `--dataset Synthetic` (+ `--synthetic_length --height --width`), `--dtype`; `--sequence`
+(+ `--batch_frames --resident_frames`): the same results with every frame forwarded once, evaluate.evaluate_sequence;
 `--output_dir` writes the predicted and target poses as a .npz instead of the reference's matplotlib figure
 and pickle.
 """
@@ -51,6 +52,15 @@ def build_parser():
     parser.add_argument("--fused_eval", action="store_true",
                         help="run the fused inference pass (model.set_eval_fused: BatchNorm, residual and ReLU in the epilogues of "
                              "the convolutions; the same poses bit for bit in fewer launches).  --dtype fp16x2m or fp16x2")
+    parser.add_argument("--sequence", action="store_true",
+                        help="sequence evaluation (geomapnet_amd.evaluate.evaluate_sequence): every frame is forwarded once, in "
+                             "batches of --batch_frames, and the windows, their VOs and the pose-graph optimisation are assembled on "
+                             "the device from that one pose per frame.  Assumes eval mode and no per-pass random transform")
+    parser.add_argument("--batch_frames", type=int, default=None, metavar="N",
+                        help="frames per forward pass of --sequence (default 192)")
+    parser.add_argument("--resident_frames", action="store_true",
+                        help="with --sequence: upload the dataset's frames to the device once (ResidentFrames.build) and feed the "
+                             "passes by index")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     return parser
@@ -68,6 +78,9 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
     if args.device_resize is not None and not args.u8_input:
         raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 frames "
                          "arrive normalised)")
+    if not args.sequence and (args.batch_frames is not None or args.resident_frames):
+        raise SystemExit("--batch_frames and --resident_frames belong to --sequence: the window loop forwards one window per pass "
+                         "from the host loader")
     if "CUDA_VISIBLE_DEVICES" not in os.environ:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.device
     G.set_compute_dtype(args.dtype)
@@ -148,9 +161,18 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
 
     # eval.py:158-163: with --pose_graph the middle prediction of a window goes to the row of ITS frame
     scatter = data_set.get_indices if (args.pose_graph and hasattr(data_set, "get_indices")) else None
-    summary, pred_poses, targ_poses = E.evaluate(model, loader, pose_m, pose_s, cuda=CUDA, pose_graph=args.pose_graph,
-                                                 fc_vos=fc_vos if windows else False, indices_of=scatter,
-                                                 length=len(data_set) if scatter else None, **sig)
+    if args.sequence:
+        if args.resident_frames:  # the frames go to the device once; the passes are fed by index
+            from geomapnet_amd.posenet import engine_of
+            from geomapnet_amd.resident import make_resident
+            (data_set,), _ = make_resident([data_set], engine_of(model).device)
+        summary, pred_poses, targ_poses = E.evaluate_sequence(
+            model, data_set, pose_m, pose_s, cuda=CUDA, pose_graph=args.pose_graph, fc_vos=fc_vos if windows else False,
+            batch_frames=192 if args.batch_frames is None else args.batch_frames, scatter=scatter is not None, **sig)
+    else:
+        summary, pred_poses, targ_poses = E.evaluate(model, loader, pose_m, pose_s, cuda=CUDA, pose_graph=args.pose_graph,
+                                                     fc_vos=fc_vos if windows else False, indices_of=scatter,
+                                                     length=len(data_set) if scatter else None, **sig)
     log("Error in translation: median {:3.2f} m,  mean {:3.2f} m\n"
         "Error in rotation: median {:3.2f} degrees, mean {:3.2f} degree".format(
             summary["median_t"], summary["mean_t"], summary["median_q"], summary["mean_q"]))
