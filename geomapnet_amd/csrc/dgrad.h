@@ -63,23 +63,15 @@ inline DgradGeom make_dgrad_geom(int B, int Hin, int Win, int cin, int cout, int
 template <typename T>
 inline void launch_conv_dgrad(const DgradGeom& d, const T* gy, const T* wd, const Epilogue& ep, hipStream_t s, const T* zero_page,
                               bool parity, bool h2 = false) {
-  if constexpr (std::is_same<T, half>::value) {
-    if (h2) {
-      if (parity && d.n_pc > 0 && (d.n_pc == 4 || ep.res == ep.out)) {
-        for (int i = 0; i < d.n_pc; ++i) {
-          const DgradParityClass& c = d.pc[i];
-          Epilogue e2 = ep;
-          e2.om_on = 1; e2.om_P = c.P; e2.om_Q = c.Q; e2.om_H = d.Hin; e2.om_W = d.Win; e2.om_a = c.a; e2.om_b = c.b;
-          e2.om_dq = make_fastdiv(c.Q);
-          e2.om_dp = make_fastdiv(c.P);
-          launch_igemm_h2(c.g, gy, wd, e2, s, zero_page);
-        }
+  auto launch = [&](const GatherGeom& g, const Epilogue& e) {
+    if constexpr (std::is_same<T, half>::value) {
+      if (h2) {
+        launch_igemm_h2(g, gy, wd, e, s, zero_page);
         return;
       }
-      launch_igemm_h2(d.full, gy, wd, ep, s, zero_page);
-      return;
     }
-  }
+    launch_igemm<T>(g, gy, wd, e, s, zero_page);
+  };
   if (parity && d.n_pc > 0 && (d.n_pc == 4 || ep.res == ep.out)) {
     for (int i = 0; i < d.n_pc; ++i) {
       const DgradParityClass& c = d.pc[i];
@@ -87,11 +79,11 @@ inline void launch_conv_dgrad(const DgradGeom& d, const T* gy, const T* wd, cons
       e2.om_on = 1; e2.om_P = c.P; e2.om_Q = c.Q; e2.om_H = d.Hin; e2.om_W = d.Win; e2.om_a = c.a; e2.om_b = c.b;
       e2.om_dq = make_fastdiv(c.Q);
       e2.om_dp = make_fastdiv(c.P);
-      launch_igemm<T>(c.g, gy, wd, e2, s, zero_page);
+      launch(c.g, e2);
     }
     return;
   }
-  launch_igemm<T>(d.full, gy, wd, ep, s, zero_page);
+  launch(d.full, ep);
 }
 
 }  // namespace mn

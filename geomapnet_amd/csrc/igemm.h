@@ -32,6 +32,7 @@
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 
@@ -136,6 +137,7 @@ inline Epilogue eval_epilogue(void* out, int ldc, const float* coef, const void*
 struct RowDiv {
   FastDiv q, p;  // divisors GatherGeom.Q and GatherGeom.P
 };
+inline RowDiv make_rowdiv(const GatherGeom& g) { return RowDiv{make_fastdiv(g.Q), make_fastdiv(g.P)}; }
 
 // Fused inference epilogue, one thread's share of a store pass: channels col .. col + 7 (col % 8 == 0) of output row `row`, the
 // staged accumulators in v.  The multiply-add is written as bn_apply_h2_kernel writes it, so that a build contracts both or neither.
@@ -934,29 +936,44 @@ inline int device_cus() {  // compute units of the current device (256 on MI355X
   return v;
 }
 
-template <typename T, int WM, int WN, int TM, int TN, int NP, int NBUF, int MINW, bool UNI = true, bool SPL = false, int ABL = 0>
+template <int V>
+using IntC = std::integral_constant<int, V>;
+#ifdef MN_ABLATION_BUILD
+// timing-experiment builds: f(IntC<V>{}) for the V of the list that equals the runtime knob `v`; -1 if none does
+template <int... Vs, typename F>
+inline int launch_ablated(int v, std::integer_sequence<int, Vs...>, F&& f) {
+  int gm = -1;
+  (void)((v == Vs && ((gm = f(IntC<Vs>{})), true)) || ...);
+  return gm;
+}
+#endif
+
+// The one launch site of igemm_kernel.  Grid and block follow from the configuration; the contraction MM from g.mma where the
+// configuration has the instantiations: the x3 forms of fp32 tensors, and -- H2, which launch_igemm_h2 alone passes, with the
+// doubled geometry -- h2 or h2q operands, or h2 operands with the fused inference epilogue (EV).  Returns the number of M-blocks.
+template <typename T, int WM, int WN, int TM, int TN, int NP, int NBUF, int MINW, bool UNI = true, bool SPL = false, int ABL = 0,
+          bool H2 = false, bool EV = false>
 inline int launch_igemm_cfg(const GatherGeom& g, const T* A, const T* Bw, const Epilogue& ep, hipStream_t stream,
                             const T* zero_page) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int gm = cdiv(g.M, BM), gn = cdiv(g.N, BN);
-  RowDiv rd;
-  rd.q = make_fastdiv(g.Q);
-  rd.p = make_fastdiv(g.P);
-  if constexpr (sizeof(T) == 4 && NP % 4 == 0 && !SPL && WM == 2 && WN == 2 && TN <= 2) {  // (the x3 configurations)
-    if (g.mma == MMA_F16X3) {
-      hipLaunchKernelGGL((igemm_kernel<T, WM, WN, TM, TN, NP, NBUF, MINW, UNI, SPL, ABL, MMA_F16X3>), dim3(gm * gn),
-                         dim3(WM * WN * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);
-      return gm;
+  auto launch = [&](auto MM) {
+    hipLaunchKernelGGL((igemm_kernel<T, WM, WN, TM, TN, NP, NBUF, MINW, UNI, SPL, ABL, decltype(MM)::value, EV>), dim3(gm * gn),
+                       dim3(WM * WN * 64), 0, stream, g, A, Bw, ep, gn, zero_page, make_rowdiv(g));
+    return gm;
+  };
+  if constexpr (H2) {
+    if constexpr (!EV) {
+      if (g.mma == MMA_H2Q) return launch(IntC<MMA_H2Q>{});
     }
-    if (g.mma == MMA_BF16X3) {
-      hipLaunchKernelGGL((igemm_kernel<T, WM, WN, TM, TN, NP, NBUF, MINW, UNI, SPL, ABL, MMA_BF16X3>), dim3(gm * gn),
-                         dim3(WM * WN * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);
-      return gm;
+    return launch(IntC<MMA_H2>{});
+  } else {
+    if constexpr (sizeof(T) == 4 && NP % 4 == 0 && !SPL && WM == 2 && WN == 2 && TN <= 2) {  // (the x3 configurations)
+      if (g.mma == MMA_F16X3) return launch(IntC<MMA_F16X3>{});
+      if (g.mma == MMA_BF16X3) return launch(IntC<MMA_BF16X3>{});
     }
+    return launch(IntC<MMA_NATIVE>{});
   }
-  hipLaunchKernelGGL((igemm_kernel<T, WM, WN, TM, TN, NP, NBUF, MINW, UNI, SPL, ABL>), dim3(gm * gn), dim3(WM * WN * 64), 0,
-                     stream, g, A, Bw, ep, gn, zero_page, rd);
-  return gm;
 }
 
 // igemm_halo.h: 288-row tiles with the A operand staged once per 64-channel chunk (fp16 3x3 stride-1 convolutions)
@@ -972,6 +989,36 @@ inline int maybe_launch_igemm_halo<half>(const GatherGeom& g, const half* A, con
   // (per launch, level 0 -> 2: layer2 114 -> 104, layer3 93 -> 81, layer4 112 -> 87 us)
   const int level = knobs().igemm_halo;
   return level > 0 ? launch_igemm_halo(g, A, Bw, ep, stream, level, tile288_wanted) : -1;
+}
+
+// The 128-row tiles of 4 waves, two workgroups per CU (configuration 1): 128x64 for N <= 64, else 128x128; 128-byte K-steps with
+// two buffers where the taps are a multiple of them (wide_k), else 64-byte K-steps with four buffers
+template <typename T>
+inline int launch_igemm_128(const GatherGeom& g, const T* A, const T* Bw, const Epilogue& ep, hipStream_t stream,
+                            const T* zero_page, bool wide_k) {
+  // channel counts that are not a multiple of the K-step (stem pixel pairs, odd test shapes): per-lane tap walk
+  if ((g.C / ElemTraits<T>::VEC) % 4 != 0) {
+    if (g.N <= 64) return launch_igemm_cfg<T, 2, 2, 2, 1, 4, 4, 2, false>(g, A, Bw, ep, stream, zero_page);
+    return launch_igemm_cfg<T, 2, 2, 2, 2, 4, 4, 2, false>(g, A, Bw, ep, stream, zero_page);
+  }
+  if (g.N <= 64) {
+    // (measured and removed for the 64-channel layers: 3-deep ring, 64-byte steps with a 4-deep ring, 256x64 tiles of
+    // 64x64 wave tiles, 2-wave workgroups of 64x64 wave tiles: 145 us -> 157..183 us on layer1)
+    if (wide_k) return launch_igemm_cfg<T, 2, 2, 2, 1, 8, 2, 2>(g, A, Bw, ep, stream, zero_page);
+    return launch_igemm_cfg<T, 2, 2, 2, 1, 4, 4, 2>(g, A, Bw, ep, stream, zero_page);
+  }
+#ifdef MN_ABLATION_BUILD
+  if constexpr (sizeof(T) == 4) {  // (the x3 main loop's experiments)
+    if (wide_k && g.mma != MMA_NATIVE) {
+      const int gm = launch_ablated(knobs().ablate, std::integer_sequence<int, 1, 2, 3, 4, 7, 8, 16, 24, 31>{}, [&](auto V) {
+        return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, decltype(V)::value>(g, A, Bw, ep, stream, zero_page);
+      });
+      if (gm >= 0) return gm;
+    }
+  }
+#endif
+  if (wide_k) return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2>(g, A, Bw, ep, stream, zero_page);
+  return launch_igemm_cfg<T, 2, 2, 2, 2, 4, 4, 2>(g, A, Bw, ep, stream, zero_page);
 }
 
 // returns the number of M-blocks used (= rows of the stats partial buffer that were written)
@@ -996,39 +1043,10 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
       const long x3_tiles128 = (long)cdiv(g.M, 128) * cdiv(g.N, 128);
       if ((g.C / VEC) % 4 == 0 && g.N % 128 == 0 && x3_tiles128 > 512 && x3_tiles128 <= 640)
         return launch_igemm_cfg<T, 2, 2, 4, 2, 4, 3, 2>(g, A, Bw, ep, stream, zero_page);
-      if ((g.C / VEC) % 4 != 0) {
-        if (g.N <= 64) return launch_igemm_cfg<T, 2, 2, 2, 1, 4, 4, 2, false>(g, A, Bw, ep, stream, zero_page);
-        return launch_igemm_cfg<T, 2, 2, 2, 2, 4, 4, 2, false>(g, A, Bw, ep, stream, zero_page);
-      }
-      if (g.N <= 64) {
-        if (wide_k) return launch_igemm_cfg<T, 2, 2, 2, 1, 8, 2, 2>(g, A, Bw, ep, stream, zero_page);
-        return launch_igemm_cfg<T, 2, 2, 2, 1, 4, 4, 2>(g, A, Bw, ep, stream, zero_page);
-      }
-#ifdef MN_ABLATION_BUILD
-      if (wide_k) {
-        switch (knobs().ablate) {
-          case 1: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 1>(g, A, Bw, ep, stream, zero_page);
-          case 2: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 2>(g, A, Bw, ep, stream, zero_page);
-          case 3: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 3>(g, A, Bw, ep, stream, zero_page);
-          case 4: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 4>(g, A, Bw, ep, stream, zero_page);
-          case 7: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 7>(g, A, Bw, ep, stream, zero_page);
-          case 8: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 8>(g, A, Bw, ep, stream, zero_page);
-          case 16: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 16>(g, A, Bw, ep, stream, zero_page);
-          case 24: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 24>(g, A, Bw, ep, stream, zero_page);
-          case 31: return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2, true, false, 31>(g, A, Bw, ep, stream, zero_page);
-          default: break;
-        }
-      }
-#endif
-      if (wide_k) return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2>(g, A, Bw, ep, stream, zero_page);
-      return launch_igemm_cfg<T, 2, 2, 2, 2, 4, 4, 2>(g, A, Bw, ep, stream, zero_page);
+      return launch_igemm_128<T>(g, A, Bw, ep, stream, zero_page, wide_k);
     }
   }
-  // channel counts that are not a multiple of the K-step (stem pixel pairs, odd test shapes): per-lane tap walk
-  if ((g.C / VEC) % 4 != 0) {
-    if (g.N <= 64) return launch_igemm_cfg<T, 2, 2, 2, 1, 4, 4, 2, false>(g, A, Bw, ep, stream, zero_page);
-    return launch_igemm_cfg<T, 2, 2, 2, 2, 4, 4, 2, false>(g, A, Bw, ep, stream, zero_page);
-  }
+  if ((g.C / VEC) % 4 != 0) return launch_igemm_128<T>(g, A, Bw, ep, stream, zero_page, wide_k);  // (per-lane tap walk)
   // per-shape default (tools/conv_bench.py on MI355X, B = 192): 128x128 tiles, two workgroups per CU (512 slots);
   // when that leaves a few tiles over one full round (layer4: 528 tiles), 256x128 tiles with 128-row wave tiles
   // put every tile in a single round instead (103 vs 121 us)
@@ -1044,12 +1062,7 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
     const int gm_halo = maybe_launch_igemm_halo<T>(g, A, Bw, ep, stream, cfg == 12 && wide_k && g.N % 256 == 0);
     if (gm_halo >= 0) return gm_halo;
   }
-  if (g.N <= 64) {
-    // (measured and removed for the 64-channel layers: 3-deep ring, 64-byte steps with a 4-deep ring, 256x64 tiles of
-    // 64x64 wave tiles, 2-wave workgroups of 64x64 wave tiles: 145 us -> 157..183 us on layer1)
-    if (wide_k) return launch_igemm_cfg<T, 2, 2, 2, 1, 8, 2, 2>(g, A, Bw, ep, stream, zero_page);
-    return launch_igemm_cfg<T, 2, 2, 2, 1, 4, 4, 2>(g, A, Bw, ep, stream, zero_page);
-  }
+  if (g.N <= 64) return launch_igemm_128<T>(g, A, Bw, ep, stream, zero_page, wide_k);
   if (cfg == 8 && g.N % 64 == 0)  // 256x128, 4 waves of 128x64, 64-byte K-steps, 3 buffers
     return launch_igemm_cfg<T, 2, 2, 4, 2, 4, 3, 2>(g, A, Bw, ep, stream, zero_page);
   // 288x256, 12 waves of 96x64, 128-byte K-steps, 2 buffers, one workgroup per CU: M = B*P*Q of the 256x341 input at
@@ -1058,19 +1071,16 @@ inline int launch_igemm(const GatherGeom& g_in, const T* A, const T* Bw, const E
   // residual 111.7 -> 103.6; the same change costs the 128x128 configuration 5 %, so it is not used there).
   if (cfg == 12 && wide_k && g.N % 256 == 0 && g.R * g.S <= 10) {  // (packed tap masks: 10 bits per A pass)
 #ifdef MN_ABLATION_BUILD
-    const int abl = knobs().ablate;
-    if (abl == 1) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 1>(g, A, Bw, ep, stream, zero_page);
-    if (abl == 2) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 2>(g, A, Bw, ep, stream, zero_page);
-    if (abl == 3) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 3>(g, A, Bw, ep, stream, zero_page);
-    if (abl == 4) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 4>(g, A, Bw, ep, stream, zero_page);
-    if (abl == 7) return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, 7>(g, A, Bw, ep, stream, zero_page);
+    const int gm = launch_ablated(knobs().ablate, std::integer_sequence<int, 1, 2, 3, 4, 7>{}, [&](auto V) {
+      return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true, decltype(V)::value>(g, A, Bw, ep, stream, zero_page);
+    });
+    if (gm >= 0) return gm;
 #endif
     return launch_igemm_cfg<T, 3, 4, 3, 2, 8, 2, 3, true, true>(g, A, Bw, ep, stream, zero_page);
   }
   // (measured and removed: the same tile with 64-byte K-steps and FOUR buffers, i.e. three tiles in flight -- 99 vs 93 us
   // on layer3, so the ring depth is not what limits it; 288x128 tiles of 6 waves, two workgroups per CU -- 131 us)
-  if (wide_k) return launch_igemm_cfg<T, 2, 2, 2, 2, 8, 2, 2>(g, A, Bw, ep, stream, zero_page);
-  return launch_igemm_cfg<T, 2, 2, 2, 2, 4, 4, 2>(g, A, Bw, ep, stream, zero_page);
+  return launch_igemm_128<T>(g, A, Bw, ep, stream, zero_page, wide_k);
 }
 
 // h2 operands (common.h MMA_H2): `g_in` describes the convolution in REAL channels; A is an h2 tensor [B][Hi][Wi][C], Bw an
@@ -1101,31 +1111,12 @@ inline int launch_igemm_h2(const GatherGeom& g_in, const half* A, const half* Bw
   g.ldb = 2 * g_in.ldb;
   g.mma = q ? MMA_H2Q : MMA_H2;
   g.tap_inner = (g.R * g.S > 1 || g.bt_on) ? 1 : 0;
-  RowDiv rd;
-  rd.q = make_fastdiv(g.Q);
-  rd.p = make_fastdiv(g.P);
   if (knobs().igemm_halo > 0) {
     const int gm_halo = launch_igemm_halo_h2<EV>(g, A, Bw, ep, stream);
     if (gm_halo >= 0) return gm_halo;
   }
-#define MN_H2_CFG(WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_)                                                                   \
-  {                                                                                                                        \
-    constexpr int BM = WM_ * TM_ * 32, BN = WN_ * TN_ * 32;                                                                \
-    const int gm = cdiv(g.M, BM), gn = cdiv(g.N, BN);                                                                      \
-    if constexpr (EV)                                                                                                      \
-      hipLaunchKernelGGL((igemm_kernel<half, WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_, true, false, 0, MMA_H2, true>), dim3(gm * gn), \
-                         dim3(WM_ * WN_ * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);                                \
-    else if (q)                                                                                                            \
-      hipLaunchKernelGGL((igemm_kernel<half, WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_, true, false, 0, MMA_H2Q>), dim3(gm * gn), \
-                         dim3(WM_ * WN_ * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);                                \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((igemm_kernel<half, WM_, WN_, TM_, TN_, NP_, NBUF_, MINW_, true, false, 0, MMA_H2>), dim3(gm * gn), \
-                         dim3(WM_ * WN_ * 64), 0, stream, g, A, Bw, ep, gn, zero_page, rd);                                \
-    return gm;                                                                                                             \
-  }
-  if (g.N <= 64) MN_H2_CFG(2, 2, 2, 1, 8, 2, 2)
-  MN_H2_CFG(2, 2, 2, 2, 8, 2, 2)
-#undef MN_H2_CFG
+  if (g.N <= 64) return launch_igemm_cfg<half, 2, 2, 2, 1, 8, 2, 2, true, false, 0, true, EV>(g, A, Bw, ep, stream, zero_page);
+  return launch_igemm_cfg<half, 2, 2, 2, 2, 8, 2, 2, true, false, 0, true, EV>(g, A, Bw, ep, stream, zero_page);
 }
 
 }  // namespace mn

@@ -516,36 +516,67 @@ inline bool igemm_halo_applies(const GatherGeom& g, const Epilogue& ep, int bn, 
          (long)g.M * g.C * 2 < 0xfffffff0l && (long)g.N * g.K * 2 < 0xfffffff0l && !ep.om_on;
 }
 
+// The one launch site of igemm_halo_kernel.  All but the shape follows from the template arguments and g: tiles of BM = WM * 96 rows
+// by BN columns, a grid of cdiv(g.M, BM) x (g.N / BN) of them, WM * WN waves, OCC from A1 (the kernel's default), Q from g.mma
+// (h2 operands without EV only: launch_igemm_h2 sets it).  Returns the number of M-blocks.
+template <int BN, int kAH, int WM, int WN, bool A1, bool H2, bool EV, int ABL = 0>
+inline int launch_halo_tile(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream) {
+  const int gm = cdiv(g.M, WM * 96), gn = g.N / BN;
+  auto launch = [&](auto Q) {
+    hipLaunchKernelGGL((igemm_halo_kernel<BN, kAH, ABL, 1, H2, WM, WN, A1, (A1 ? 2 : 1), decltype(Q)::value, EV>), dim3(gm * gn),
+                       dim3(WM * WN * 64), 0, stream, g, A, Bw, ep, gn, make_rowdiv(g));
+    return gm;
+  };
+  if constexpr (H2 && !EV) {
+    if (g.mma == MMA_H2Q) return launch(std::true_type{});
+  }
+  return launch(std::false_type{});
+}
+#ifdef MN_ABLATION_BUILD
+// MN_HALO_ABLATE: the timing-experiment instantiation of one of the two 12-wave fp16 shapes, or -1 where the knob names none
+template <int BN, int kAH>
+inline int launch_halo_ablated(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream) {
+  return launch_ablated(knobs().halo_ablate, std::integer_sequence<int, 1, 2, 3, 4, 8, 16, 12, 20, 24, 28>{}, [&](auto V) {
+    return launch_halo_tile<BN, kAH, 3, 4, false, false, false, decltype(V)::value>(g, A, Bw, ep, stream);
+  });
+}
+#endif
+
+// Tile-filling predicates of the 128-column shapes, shared by the two dispatchers below.
+// At least two rounds of 192-row tiles at two workgroups per CU:
+inline bool two_rounds_of_192(const GatherGeom& g) { return (long)cdiv(g.M, 192) * (g.N / 128) >= 2L * device_cus(); }
+// 384-row tiles fill the chip's rounds about as well as 288-row tiles do (efficiency = tiles / slots of the rounds they occupy):
+inline bool fills_rounds_like_288(const GatherGeom& g) {
+  const int cus = device_cus();
+  auto fill = [&](int bm) {
+    const long tiles = (long)cdiv(g.M, bm) * (g.N / 128);
+    return (double)tiles / ((double)cdiv(tiles, cus) * cus);
+  };
+  return fill(384) >= fill(288) - 0.03;
+}
+
+// Two dispatchers, fp16 and h2 operands.  Each is a chain of `if (condition) return launch_halo_tile<shape>`; the first shape whose
+// condition holds runs, -1 = the launch is not taken.  Their conditions differ in four ways that are behaviour, not accident:
+//   * the fp16 form gates its shapes by `level` (knobs().igemm_halo) and by tile288_wanted (igemm.h's own choice of its 288x256
+//     tile); the h2 form decides the 256-column shape from its own tile count or knobs().h2_halo256;
+//   * only the fp16 form keeps the 256-column shape from a launch when halo_a1 == 2 (the 192-row tile forced);
+//   * only the fp16 form reads knobs().halo384 (0 never, 2 always); the h2 form takes the 384-row tile by the fill rule alone;
+//   * only the h2 form has the 64-column shape of layer1, <64, 368, A1> (fp16 layer1 goes to halo_pp.h).
+//
 // level (knobs().igemm_halo): 1 = the 256-column shape where igemm.h would pick its own 288x256 tile (layer3 at 192 images, or a
 // forced MN_IGEMM_CONFIG=12); 2 = additionally the 128-column shape for every other launch it covers (layers 2 and 4).
 // Returns the number of M-blocks used (rows of a [grid_m][2][N] statistics buffer), or -1 if the launch is not taken.
 inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream,
                              int level, bool tile288_wanted) {
-  const int gm = cdiv(g.M, 288);
-  RowDiv rd;
-  rd.q = make_fastdiv(g.Q);
-  rd.p = make_fastdiv(g.P);
-#ifdef MN_ABLATION_BUILD
-  const int abl = knobs().halo_ablate;
-#endif
   // (the 192-row tile switched off for the plain-fp16 launches alone -- in the fp16x2m mode those are the data gradients, whose 70 KB
   //  form shares a CU with a weight-gradient workgroup of the side stream: measured, not kept,
   //  profiles/r06/c21_c22_co_residency_and_xcd_order_experiments.txt)
   const int a1 = knobs().halo_a1;
   if (level >= 1 && tile288_wanted && a1 != 2 && igemm_halo_applies(g, ep, 256, 352)) {
 #ifdef MN_ABLATION_BUILD
-#define MN_HALO_ABL(BN_, AH_, V_)                                                                                          \
-  if (abl == V_) {                                                                                                         \
-    hipLaunchKernelGGL((igemm_halo_kernel<BN_, AH_, V_>), dim3(gm * (g.N / BN_)), dim3(768), 0, stream, g, A, Bw, ep,      \
-                       g.N / BN_, rd);                                                                                     \
-    return gm;                                                                                                             \
-  }
-    MN_HALO_ABL(256, 352, 1) MN_HALO_ABL(256, 352, 2) MN_HALO_ABL(256, 352, 3) MN_HALO_ABL(256, 352, 4)
-    MN_HALO_ABL(256, 352, 8) MN_HALO_ABL(256, 352, 16) MN_HALO_ABL(256, 352, 12) MN_HALO_ABL(256, 352, 20)
-    MN_HALO_ABL(256, 352, 24) MN_HALO_ABL(256, 352, 28)
+    if (const int gm = launch_halo_ablated<256, 352>(g, A, Bw, ep, stream); gm >= 0) return gm;
 #endif
-    hipLaunchKernelGGL((igemm_halo_kernel<256, 352>), dim3(gm * (g.N / 256)), dim3(768), 0, stream, g, A, Bw, ep, g.N / 256, rd);
-    return gm;
+    return launch_halo_tile<256, 352, 3, 4, false, false, false>(g, A, Bw, ep, stream);
   }
   // 192-row tiles of 4 waves (2 x 2 of 96 x 64) with ONE A image (the next chunk's image requested after the chunk's last K-step):
   // 70 KB of LDS, so two workgroups share a CU and each one's prologue / image reload / epilogue runs under the other's MFMAs --
@@ -554,37 +585,21 @@ inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw,
   // step 13.22 -> 13.16 ms; fp16x2 224 -> 202, 218 -> 199, 282 -> 250 us, step 28.82 -> 28.55 ms (profiles/r04/c30_*).
   // For layers 3 and 4 (704 / 352 such tiles: 1.4 / 0.7 rounds) it loses to their one-round shapes: fp16 76 -> 85 and 81 -> 88 us,
   // fp16x2 191 -> 207 and 223 -> 234 us (call 31).  a1 (knobs().halo_a1): 0 off, 2 always
-  if (level >= 2 && a1 > 0 && (a1 == 2 || (long)cdiv(g.M, 192) * (g.N / 128) >= 2L * device_cus()) &&
-      igemm_halo_applies(g, ep, 128, 288, 192)) {
-    hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, false, 2, 2, true>), dim3(cdiv(g.M, 192) * (g.N / 128)), dim3(256), 0, stream, g,
-                       A, Bw, ep, g.N / 128, rd);
-    return cdiv(g.M, 192);
-  }
+  if (level >= 2 && a1 > 0 && (a1 == 2 || two_rounds_of_192(g)) && igemm_halo_applies(g, ep, 128, 288, 192))
+    return launch_halo_tile<128, 288, 2, 2, true, false, false>(g, A, Bw, ep, stream);
   // (layer1 in fp16 on this shape with 64 columns, measured and removed: 132.5 us forward / 134.8 data gradient against 112.8 / 111.1
   //  for halo_pp.h's persistent kernel with resident weights; whole step 13.32 -> 13.63 ms, profiles/r04/c34_*)
   // the 8-wave 384-row tile of 96 x 64 wave tiles where it fills the chip's rounds as well as the 288-row tile does (layer2 at 192
   // images: 688 tiles = 2.69 rounds against 918 = 3.59): 0.55 instead of 0.89 fragment reads per MFMA; layer2 forward 99.3 -> 92.7
   // us, data gradient 97.2 -> 90.5, whole step 13.95 -> 13.79 ms (round 4, profiles/r04/c28_*).  bm384: 0 never, 2 always.
   const int bm384 = knobs().halo384;
-  if (level >= 2 && bm384 > 0 && igemm_halo_applies(g, ep, 128, 480, 384)) {
-    const long t384 = (long)cdiv(g.M, 384) * (g.N / 128), t288 = (long)gm * (g.N / 128);
-    const int cus = device_cus();
-    const double e384 = (double)t384 / ((double)cdiv(t384, cus) * cus), e288 = (double)t288 / ((double)cdiv(t288, cus) * cus);
-    if (bm384 == 2 || e384 >= e288 - 0.03) {
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, false, 4, 2>), dim3(cdiv(g.M, 384) * (g.N / 128)), dim3(512), 0, stream, g, A,
-                         Bw, ep, g.N / 128, rd);
-      return cdiv(g.M, 384);
-    }
-  }
+  if (level >= 2 && bm384 > 0 && igemm_halo_applies(g, ep, 128, 480, 384) && (bm384 == 2 || fills_rounds_like_288(g)))
+    return launch_halo_tile<128, 480, 4, 2, false, false, false>(g, A, Bw, ep, stream);
   if (level >= 2 && igemm_halo_applies(g, ep, 128, 384)) {
 #ifdef MN_ABLATION_BUILD
-    MN_HALO_ABL(128, 384, 1) MN_HALO_ABL(128, 384, 2) MN_HALO_ABL(128, 384, 3) MN_HALO_ABL(128, 384, 4)
-    MN_HALO_ABL(128, 384, 8) MN_HALO_ABL(128, 384, 16) MN_HALO_ABL(128, 384, 12) MN_HALO_ABL(128, 384, 20)
-    MN_HALO_ABL(128, 384, 24) MN_HALO_ABL(128, 384, 28)
-#undef MN_HALO_ABL
+    if (const int gm = launch_halo_ablated<128, 384>(g, A, Bw, ep, stream); gm >= 0) return gm;
 #endif
-    hipLaunchKernelGGL((igemm_halo_kernel<128, 384>), dim3(gm * (g.N / 128)), dim3(768), 0, stream, g, A, Bw, ep, g.N / 128, rd);
-    return gm;
+    return launch_halo_tile<128, 384, 3, 4, false, false, false>(g, A, Bw, ep, stream);
   }
   return -1;
 }
@@ -601,86 +616,24 @@ inline int launch_igemm_halo(const GatherGeom& g, const half* A, const half* Bw,
 // EV: the fused inference epilogue; the same choice for both forms (igemm.h launch_igemm_h2)
 template <bool EV>
 inline int launch_igemm_halo_h2(const GatherGeom& g2, const half* A, const half* Bw, const Epilogue& ep, hipStream_t stream) {
-  const int gm = cdiv(g2.M, 288);
-  const bool q = g2.mma == MMA_H2Q;  // h2q operands: the scaled-fp8 cross terms (igemm_halo_kernel Q)
-  RowDiv rd;
-  rd.q = make_fastdiv(g2.Q);
-  rd.p = make_fastdiv(g2.P);
-  const long tiles288 = (long)gm * (g2.N / 256);
+  const long tiles288 = (long)cdiv(g2.M, 288) * (g2.N / 256);
   const bool force256 = knobs().h2_halo256;
   const int a1 = knobs().halo_a1;  // (see launch_igemm_halo)
-  if (g2.N % 256 == 0 && ((tiles288 > 192 && tiles288 <= device_cus()) || force256) && igemm_halo_applies(g2, ep, 256, 352)) {
-    if constexpr (EV)
-      hipLaunchKernelGGL((igemm_halo_kernel<256, 352, 0, 1, true, 3, 4, false, 1, false, true>), dim3(gm * (g2.N / 256)), dim3(768), 0, stream, g2, A, Bw, ep,
-                       g2.N / 256, rd);
-    else if (q)
-      hipLaunchKernelGGL((igemm_halo_kernel<256, 352, 0, 1, true, 3, 4, false, 1, true>), dim3(gm * (g2.N / 256)), dim3(768), 0, stream, g2, A, Bw, ep,
-                       g2.N / 256, rd);
-    else
-      hipLaunchKernelGGL((igemm_halo_kernel<256, 352, 0, 1, true>), dim3(gm * (g2.N / 256)), dim3(768), 0, stream, g2, A, Bw, ep,
-                       g2.N / 256, rd);
-    return gm;
-  }
+  if (g2.N % 256 == 0 && ((tiles288 > 192 && tiles288 <= device_cus()) || force256) && igemm_halo_applies(g2, ep, 256, 352))
+    return launch_halo_tile<256, 352, 3, 4, false, true, EV>(g2, A, Bw, ep, stream);
   // layer1 (64 -> 64 channels, rows of up to 87 pixels): 192-row tiles of 4 waves, one A image, two workgroups per CU
   // (measured: 338 -> 304 us forward, 356 -> 326 data gradient, step 29.69 -> 29.52 ms; 288-row tiles of 6 waves at two workgroups
   //  per CU -- 27 % less DMA per row -- 409 us: six waves do not spread over four SIMDs; profiles/r04/c15_*, c16_*)
-  if (g2.N == 64 && igemm_halo_applies(g2, ep, 64, 368, 192)) {
-    if constexpr (EV)
-      hipLaunchKernelGGL((igemm_halo_kernel<64, 368, 0, 1, true, 2, 2, true, 2, false, true>), dim3(cdiv(g2.M, 192)), dim3(256), 0, stream, g2, A, Bw, ep, 1,
-                       rd);
-    else if (q)
-      hipLaunchKernelGGL((igemm_halo_kernel<64, 368, 0, 1, true, 2, 2, true, 2, true>), dim3(cdiv(g2.M, 192)), dim3(256), 0, stream, g2, A, Bw, ep, 1,
-                       rd);
-    else
-      hipLaunchKernelGGL((igemm_halo_kernel<64, 368, 0, 1, true, 2, 2, true>), dim3(cdiv(g2.M, 192)), dim3(256), 0, stream, g2, A, Bw, ep, 1,
-                       rd);
-    return cdiv(g2.M, 192);
-  }
+  if (g2.N == 64 && igemm_halo_applies(g2, ep, 64, 368, 192))
+    return launch_halo_tile<64, 368, 2, 2, true, true, EV>(g2, A, Bw, ep, stream);
   // layer1's two-workgroup shape for the 128-column layers with at least two rounds of 192-row tiles (layer2): see launch_igemm_halo
-  if (a1 > 0 && g2.N % 128 == 0 && (a1 == 2 || (long)cdiv(g2.M, 192) * (g2.N / 128) >= 2L * device_cus()) &&
-      igemm_halo_applies(g2, ep, 128, 288, 192)) {
-    if constexpr (EV)
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, true, 2, 2, true, 2, false, true>), dim3(cdiv(g2.M, 192) * (g2.N / 128)), dim3(256), 0, stream,
-                       g2, A, Bw, ep, g2.N / 128, rd);
-    else if (q)
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, true, 2, 2, true, 2, true>), dim3(cdiv(g2.M, 192) * (g2.N / 128)), dim3(256), 0, stream,
-                       g2, A, Bw, ep, g2.N / 128, rd);
-    else
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 288, 0, 1, true, 2, 2, true>), dim3(cdiv(g2.M, 192) * (g2.N / 128)), dim3(256), 0, stream,
-                       g2, A, Bw, ep, g2.N / 128, rd);
-    return cdiv(g2.M, 192);
-  }
+  if (a1 > 0 && g2.N % 128 == 0 && (a1 == 2 || two_rounds_of_192(g2)) && igemm_halo_applies(g2, ep, 128, 288, 192))
+    return launch_halo_tile<128, 288, 2, 2, true, true, EV>(g2, A, Bw, ep, stream);
   // 128-column layers: the 8-wave 384-row tile where it fills the chip's rounds about as well as the 288-row tile does (layer2 at
   // 192 images: 688 tiles = 2.69 rounds against 918 = 3.59; layer4: 176 tiles = 0.69 of a round against 236 = 0.92 -> 288 rows)
-  if (igemm_halo_applies(g2, ep, 128, 480, 384)) {
-    const long t384 = (long)cdiv(g2.M, 384) * (g2.N / 128), t288 = (long)gm * (g2.N / 128);
-    const int cus = device_cus();
-    const double e384 = (double)t384 / ((double)cdiv(t384, cus) * cus), e288 = (double)t288 / ((double)cdiv(t288, cus) * cus);
-    if (e384 >= e288 - 0.03) {
-    if constexpr (EV)
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, true, 4, 2, false, 1, false, true>), dim3(cdiv(g2.M, 384) * (g2.N / 128)), dim3(512), 0, stream, g2,
-                         A, Bw, ep, g2.N / 128, rd);
-    else if (q)
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, true, 4, 2, false, 1, true>), dim3(cdiv(g2.M, 384) * (g2.N / 128)), dim3(512), 0, stream, g2,
-                         A, Bw, ep, g2.N / 128, rd);
-    else
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 480, 0, 1, true, 4, 2>), dim3(cdiv(g2.M, 384) * (g2.N / 128)), dim3(512), 0, stream, g2,
-                         A, Bw, ep, g2.N / 128, rd);
-      return cdiv(g2.M, 384);
-    }
-  }
-  if (igemm_halo_applies(g2, ep, 128, 384)) {
-    if constexpr (EV)
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 384, 0, 1, true, 3, 4, false, 1, false, true>), dim3(gm * (g2.N / 128)), dim3(768), 0, stream, g2, A, Bw, ep,
-                       g2.N / 128, rd);
-    else if (q)
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 384, 0, 1, true, 3, 4, false, 1, true>), dim3(gm * (g2.N / 128)), dim3(768), 0, stream, g2, A, Bw, ep,
-                       g2.N / 128, rd);
-    else
-      hipLaunchKernelGGL((igemm_halo_kernel<128, 384, 0, 1, true>), dim3(gm * (g2.N / 128)), dim3(768), 0, stream, g2, A, Bw, ep,
-                       g2.N / 128, rd);
-    return gm;
-  }
+  if (igemm_halo_applies(g2, ep, 128, 480, 384) && fills_rounds_like_288(g2))
+    return launch_halo_tile<128, 480, 4, 2, false, true, EV>(g2, A, Bw, ep, stream);
+  if (igemm_halo_applies(g2, ep, 128, 384)) return launch_halo_tile<128, 384, 3, 4, false, true, EV>(g2, A, Bw, ep, stream);
   return -1;
 }
 

@@ -726,6 +726,19 @@ static __global__ void __launch_bounds__(256, 2) wgrad_x3_kernel(WgradArgs a) {
     }
 }
 
+// the (bmo, bno) tile of the split-K kernels, each 64 or 128, as compile-time constants: f(IntC<BMO>{}, IntC<BNO>{})
+template <typename F>
+inline void with_wgrad_tile(int bmo, int bno, F&& f) {
+  if (bmo == 64 && bno == 64)
+    f(IntC<64>{}, IntC<64>{});
+  else if (bmo == 64)
+    f(IntC<64>{}, IntC<128>{});
+  else if (bno == 64)
+    f(IntC<128>{}, IntC<64>{});
+  else
+    f(IntC<128>{}, IntC<128>{});
+}
+
 template <typename T>
 struct WgradDma {
   static bool launch(const WgradArgs&, dim3, int, int, hipStream_t, const void*) { return false; }
@@ -741,25 +754,15 @@ struct WgradDma<half> {
                       (long)g.M * x_row_halves(a.x_h2, g.C) * 2 < 0xfffffff0l;
     // fast form: transpose reads from inline assembly with hand-placed waits (ASMRD above); measured on MI355X (round 2):
     // layer1 189 -> 155 us, layer2 140 -> 122, layer3 144 -> 124, layer4 129 -> 117 against the builtin reads
-    if (fast) {
-      if (bmo == 64 && bno == 64)
-        hipLaunchKernelGGL((wgrad_dma_kernel<64, 64, BKM, MINW, true, true>), grid, block, 0, stream, a, zp);
-      else if (bmo == 64)
-        hipLaunchKernelGGL((wgrad_dma_kernel<64, 128, BKM, MINW, true, true>), grid, block, 0, stream, a, zp);
-      else if (bno == 64)
-        hipLaunchKernelGGL((wgrad_dma_kernel<128, 64, BKM, MINW, true, true>), grid, block, 0, stream, a, zp);
-      else  // (the 128x128 tile needs more than the 128 registers of 4 waves per SIMD: 3 requested = what it runs at)
-        hipLaunchKernelGGL((wgrad_dma_kernel<128, 128, BKM, (MINW > 3 ? 3 : MINW), true, true>), grid, block, 0, stream, a, zp);
-      return;
-    }
-    if (bmo == 64 && bno == 64)
-      hipLaunchKernelGGL((wgrad_dma_kernel<64, 64, BKM, MINW, false>), grid, block, 0, stream, a, zp);
-    else if (bmo == 64)
-      hipLaunchKernelGGL((wgrad_dma_kernel<64, 128, BKM, MINW, false>), grid, block, 0, stream, a, zp);
-    else if (bno == 64)
-      hipLaunchKernelGGL((wgrad_dma_kernel<128, 64, BKM, MINW, false>), grid, block, 0, stream, a, zp);
-    else
-      hipLaunchKernelGGL((wgrad_dma_kernel<128, 128, BKM, MINW, false>), grid, block, 0, stream, a, zp);
+    with_wgrad_tile(bmo, bno, [&](auto BMO, auto BNO) {
+      constexpr int bm = decltype(BMO)::value, bn = decltype(BNO)::value;
+      // (the 128x128 tile needs more than the 128 registers of 4 waves per SIMD: 3 requested = what it runs at)
+      constexpr int MINW_FAST = (bm == 128 && bn == 128) ? (MINW > 3 ? 3 : MINW) : MINW;
+      if (fast)
+        hipLaunchKernelGGL((wgrad_dma_kernel<bm, bn, BKM, MINW_FAST, true, true>), grid, block, 0, stream, a, zp);
+      else
+        hipLaunchKernelGGL((wgrad_dma_kernel<bm, bn, BKM, MINW, false>), grid, block, 0, stream, a, zp);
+    });
   }
   static bool launch(const WgradArgs& a, dim3 grid3, int bmo, int bno, hipStream_t stream, const void* zero_page) {
     const half* zp = reinterpret_cast<const half*>(zero_page);
@@ -840,34 +843,19 @@ inline void launch_wgrad(WgradArgs a, int target_blocks, hipStream_t stream, con
   }
   dim3 grid(cdiv(g.N, bmo), cdiv(g.K, bno), splits), block(256);
   if (sizeof(T) == 2 && g.mma == MMA_H2) {
-    if (bmo == 64 && bno == 64)
-      hipLaunchKernelGGL((wgrad_x3_kernel<64, 64, true>), grid, block, 0, stream, a);
-    else if (bmo == 64)
-      hipLaunchKernelGGL((wgrad_x3_kernel<64, 128, true>), grid, block, 0, stream, a);
-    else if (bno == 64)
-      hipLaunchKernelGGL((wgrad_x3_kernel<128, 64, true>), grid, block, 0, stream, a);
-    else
-      hipLaunchKernelGGL((wgrad_x3_kernel<128, 128, true>), grid, block, 0, stream, a);
+    with_wgrad_tile(bmo, bno, [&](auto BMO, auto BNO) {
+      hipLaunchKernelGGL((wgrad_x3_kernel<decltype(BMO)::value, decltype(BNO)::value, true>), grid, block, 0, stream, a);
+    });
   } else if (sizeof(T) == 4 && g.mma == MMA_BF16X3) {
-    if constexpr (sizeof(T) == 4) {
-      if (bmo == 64 && bno == 64)
-        hipLaunchKernelGGL((wgrad_x3_kernel<64, 64>), grid, block, 0, stream, a);
-      else if (bmo == 64)
-        hipLaunchKernelGGL((wgrad_x3_kernel<64, 128>), grid, block, 0, stream, a);
-      else if (bno == 64)
-        hipLaunchKernelGGL((wgrad_x3_kernel<128, 64>), grid, block, 0, stream, a);
-      else
-        hipLaunchKernelGGL((wgrad_x3_kernel<128, 128>), grid, block, 0, stream, a);
-    }
-  } else if (WgradDma<T>::launch(a, grid, bmo, bno, stream, zero_page)) {
-  } else if (bmo == 64 && bno == 64)
-    hipLaunchKernelGGL((wgrad_kernel<T, 64, 64>), grid, block, 0, stream, a);
-  else if (bmo == 64)
-    hipLaunchKernelGGL((wgrad_kernel<T, 64, 128>), grid, block, 0, stream, a);
-  else if (bno == 64)
-    hipLaunchKernelGGL((wgrad_kernel<T, 128, 64>), grid, block, 0, stream, a);
-  else
-    hipLaunchKernelGGL((wgrad_kernel<T, 128, 128>), grid, block, 0, stream, a);
+    if constexpr (sizeof(T) == 4)
+      with_wgrad_tile(bmo, bno, [&](auto BMO, auto BNO) {
+        hipLaunchKernelGGL((wgrad_x3_kernel<decltype(BMO)::value, decltype(BNO)::value>), grid, block, 0, stream, a);
+      });
+  } else if (!WgradDma<T>::launch(a, grid, bmo, bno, stream, zero_page)) {
+    with_wgrad_tile(bmo, bno, [&](auto BMO, auto BNO) {
+      hipLaunchKernelGGL((wgrad_kernel<T, decltype(BMO)::value, decltype(BNO)::value>), grid, block, 0, stream, a);
+    });
+  }
   if (sliced)
     hipLaunchKernelGGL(wgrad_split_reduce_kernel, dim3((unsigned)cdiv((int)((slice + 255) / 256), 1)), dim3(256), 0, stream,
                        (const float*)a.ws, dW_final, slice, splits, slice);
