@@ -136,6 +136,8 @@ _PROTOS = {
     "mn_op_resize_tile": (c_i, [c_i, c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
     "mn_op_gather_frames": (c_i, [c_void, c_void, c_void, c_i64, c_i, c_i64, c_void, c_void]),
     "mn_op_resize_u8_indexed": (c_i, [c_void, c_void, c_i64, c_void, c_void, c_i, c_i, c_i, c_i, c_i, c_void, c_void]),
+    "mn_op_frame_stats_u8": (c_i, [c_void, c_void, c_i64, c_i, c_i, c_i, c_void, c_i, c_i, c_void, c_void, c_void]),
+    "mn_op_frame_stats_work_bytes": (c_i64, [c_i, c_i, c_i, c_i]),
     "mn_op_stem_dgrad": (c_i, [c_i, c_void, c_void, c_void, c_i, c_i, c_i, c_f, c_void]),
     "mn_op_bn_eval_bwd": (c_i, [c_i, c_void, c_void, c_void, c_void, c_i64, c_i, c_void]),
     "mn_op_saliency": (c_i, [c_void, c_void, c_void, c_void, c_i, c_i, c_i, c_void]),

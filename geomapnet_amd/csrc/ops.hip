@@ -7,6 +7,7 @@
 #include "criterion.h"
 #include "elementwise.h"
 #include "elementwise_h2.h"
+#include "frame_stats.h"
 #include "head.h"
 #include "jitter.h"
 #include "knobs.h"
@@ -703,6 +704,32 @@ extern "C" int mn_op_gather_frames(const void* store, const int32_t* index, void
   if (bad_flag) hipMemsetAsync(bad_flag, 0, sizeof(float), (hipStream_t)stream);
   launch_gather_frames(store, index, out, (long)frame_bytes, images, (long)store_frames, bad_flag, (hipStream_t)stream);
   return check_launch("gather_frames");
+}
+
+extern "C" int64_t mn_op_frame_stats_work_bytes(int images, int H, int W, int blocks) {
+  if (images < 1 || H < 1 || W < 1 || blocks < 0) {
+    fail("mn_op_frame_stats_work_bytes: images, H and W must be positive and blocks >= 0");
+    return -1;
+  }
+  return frame_stats_blocks(images, (long)H * W * 3, blocks, device_cus()) * 6 * (int64_t)sizeof(u64);
+}
+
+extern "C" int mn_op_frame_stats_u8(const unsigned char* frames, const int32_t* index, int64_t store_frames, int images, int H, int W,
+                                    uint64_t* sums, int accumulate, int blocks, void* work, float* bad_flag, void* stream) {
+  begin_op();
+  if (!frames || !sums || !work) return fail("mn_op_frame_stats_u8: frames, sums and work are required");
+  if (((uintptr_t)sums & 7) != 0 || ((uintptr_t)work & 7) != 0)
+    return fail("mn_op_frame_stats_u8: sums (device uint64 [6]) and work must be 8-byte aligned");
+  if (index && ((uintptr_t)index & 3) != 0) return fail("mn_op_frame_stats_u8: index (device int32 [images]) must be 4-byte aligned");
+  if (images < 1 || H < 1 || W < 1) return fail("mn_op_frame_stats_u8: images, H and W must be positive");
+  if (index && store_frames < 1) return fail("mn_op_frame_stats_u8: store_frames must be at least 1 with an index");
+  if (blocks < 0) return fail("mn_op_frame_stats_u8: blocks must be >= 0 (0: the default grid)");
+  const long L = (long)H * W * 3;
+  const long nb = frame_stats_blocks(images, L, blocks, device_cus());
+  if (index && bad_flag) hipMemsetAsync(bad_flag, 0, sizeof(float), (hipStream_t)stream);
+  launch_frame_stats(frames, index, (long)store_frames, images, L, (u64*)sums, accumulate != 0, nb, (u64*)work, bad_flag,
+                     (hipStream_t)stream);
+  return check_launch("frame_stats_u8");
 }
 
 extern "C" int mn_op_stem_dgrad(int dtype, const void* gy, const void* w, float* gx, int B, int H, int W, float alpha, void* stream) {

@@ -574,6 +574,19 @@ int mn_op_gather_frames(const void* store, const int32_t* index, void* out, int6
 int mn_op_resize_u8_indexed(const unsigned char* store, const int32_t* index, int64_t store_frames, unsigned char* out, void* work,
                             int B, int src_h, int src_w, int H, int W, float* bad_flag, void* stream);
 
+/* Pixel statistics of uint8 frames (what the reference's scripts/dataset_mean.py accumulates on the host for stats.txt):
+ * sums[0..2] = per-channel sum, sums[3..5] = per-channel sum of squares of the bytes of `images` NHWC frames [images][H][W][3], as
+ * unsigned 64-bit integers in device memory (8-byte aligned) -- exact, and independent of the grid.  index NULL: `frames` holds the
+ * images, at any byte alignment; else `frames` is a store [store_frames][H][W][3] and image b is frame index[b] (device int32
+ * [images]); bad_flag (device float, may be NULL) is then cleared ahead of the kernel and set to 1 if an index lies outside
+ * [0, store_frames): that image counts frame 0.  accumulate != 0 adds to what `sums` holds (a dataset taken chunk by chunk, no host
+ * round trip); 0 overwrites it.  blocks: workgroups of the first launch, 0 = the default (tests, tuning; never more than the frames
+ * have 12 KiB units).  work: mn_op_frame_stats_work_bytes(images, H, W, blocks) bytes of device memory, 8-byte aligned (the
+ * workgroups' partial sums; a second launch folds them -- no atomics).  Only bytes of the frames are read. */
+int mn_op_frame_stats_u8(const unsigned char* frames, const int32_t* index, int64_t store_frames, int images, int H, int W,
+                         uint64_t* sums, int accumulate, int blocks, void* work, float* bad_flag, void* stream);
+int64_t mn_op_frame_stats_work_bytes(int images, int H, int W, int blocks);
+
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (no counterpart in the reference, which is single-device: common/train.py:91-92).
  * Stand-in for the reduction workgroups of an RCCL ring all-reduce on a one-GPU box: `workgroups` x `threads` stay resident

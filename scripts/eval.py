@@ -49,6 +49,10 @@ def build_parser():
                         help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
                              "transform): the dataset yields frames of --height x --width and the network runs at the resized "
                              "size; needs --u8_input")
+    parser.add_argument("--stats_file", type=str, default=None, metavar="PATH",
+                        help="the Normalize constants of --u8_input from PATH, a stats.txt as scripts/dataset_mean.py writes it "
+                             "(row 0 the mean, row 1 the variance; the reference's eval.py:100-101) instead of the synthetic set's; "
+                             "needs --u8_input")
     parser.add_argument("--fused_eval", action="store_true",
                         help="run the fused inference pass (model.set_eval_fused: BatchNorm, residual and ReLU in the epilogues of "
                              "the convolutions; the same poses bit for bit in fewer launches).  --dtype fp16x2m or fp16x2")
@@ -78,6 +82,9 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
     if args.device_resize is not None and not args.u8_input:
         raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 frames "
                          "arrive normalised)")
+    if args.stats_file is not None and not args.u8_input:
+        raise SystemExit("--stats_file needs --u8_input: the statistics are those of uint8 frames, for the Normalize of the device's "
+                         "input conversion (fp32 frames arrive normalised)")
     if not args.sequence and (args.batch_frames is not None or args.resident_frames):
         raise SystemExit("--batch_frames and --resident_frames belong to --sequence: the window loop forwards one window per pass "
                          "from the host loader")
@@ -113,7 +120,8 @@ def run(args, dataset=None, pose_stats=None, _binding=None, log=print):
         model = posenet
     model.eval()
     if args.u8_input:
-        model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
+        mean, std = G.read_stats(args.stats_file) if args.stats_file is not None else (SyntheticFrames.MEAN, SyntheticFrames.STD)
+        model.set_input_u8(mean, std)
     if args.device_resize is not None:
         model.set_input_resize(args.device_resize)
     if args.fused_eval:

@@ -40,6 +40,9 @@ def build_parser():
                         help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
                              "transform): the dataset yields frames of --height x --width and the network runs at the resized "
                              "size; needs --u8_input")
+    parser.add_argument("--stats_file", type=str, default=None, metavar="PATH",
+                        help="the Normalize constants of --u8_input from PATH, a stats.txt as scripts/dataset_mean.py writes it "
+                             "(row 0 the mean, row 1 the variance) instead of the synthetic set's; needs --u8_input")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=341)
     return parser
@@ -47,7 +50,7 @@ def build_parser():
 
 def run(args, dataset=None, stats=None, _binding=None, log=print):
     """returns the list of PNG files written.  dataset: frames as (image, pose) pairs; stats: (mean[3], std[3]) of its Normalize
-    (the scene's stats.txt in the reference)"""
+    (the scene's stats.txt in the reference; given, it takes the place of --stats_file)"""
     import numpy as np
     import torch
     from PIL import Image
@@ -59,6 +62,9 @@ def run(args, dataset=None, stats=None, _binding=None, log=print):
     if args.device_resize is not None and not args.u8_input:
         raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 frames "
                          "arrive normalised)")
+    if args.stats_file is not None and not args.u8_input:
+        raise SystemExit("--stats_file needs --u8_input: the statistics are those of uint8 frames, for the Normalize of the device's "
+                         "input conversion (fp32 frames arrive normalised)")
     if "CUDA_VISIBLE_DEVICES" not in os.environ:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.device
     G.set_compute_dtype(args.dtype)
@@ -74,7 +80,12 @@ def run(args, dataset=None, stats=None, _binding=None, log=print):
     feature_extractor = G.resnet34(pretrained=False, **kw)
     model = G.PoseNet(feature_extractor, droprate=dropout, pretrained=False, **kw)
     model.eval()
-    mean, std = stats if stats is not None else (SyntheticFrames.MEAN, SyntheticFrames.STD)
+    if stats is not None:
+        mean, std = stats
+    elif args.stats_file is not None:
+        mean, std = G.read_stats(args.stats_file)
+    else:
+        mean, std = SyntheticFrames.MEAN, SyntheticFrames.STD
     if args.u8_input:
         model.set_input_u8(mean, std)
     if args.device_resize is not None:

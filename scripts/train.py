@@ -12,6 +12,8 @@ Trainer.train_val.  Differences, all additive:
 * `--dtype fp16|fp32` selects the compute precision of the HIP kernels (fp16 storage + fp32 accumulate, or the
   fp32 parity build).
 * `--epochs`, `--batch_size`, `--logdir` override the config file (smoke runs).
+* `--stats_file PATH` / `--stats_from_frames` (with `--u8_input`): the Normalize constants from a stats.txt (the reference's
+  train.py:126-127), or computed from the training frames on the device before training and written to <logdir>/stats.txt.
 * launched under `python -m torch.distributed.run --nproc-per-node N scripts/train.py ...` it trains data
   parallel: one process per GPU, windows sharded, gradient buckets all-reduced over RCCL during backward.
 """
@@ -74,6 +76,14 @@ def build_parser():
                         help="torchvision's Resize(SIZE) on the device (PIL's bilinear resample, bit for bit; the reference's "
                              "transform, scripts/train.py:120): the dataset yields frames of --height x --width and the network runs "
                              "at the resized size; needs --u8_input")
+    parser.add_argument("--stats_file", type=str, default=None, metavar="PATH",
+                        help="the Normalize constants of --u8_input from PATH, a stats.txt as scripts/dataset_mean.py writes it "
+                             "(row 0 the mean, row 1 the variance; the reference's train.py:126-127) instead of the synthetic set's; "
+                             "needs --u8_input")
+    parser.add_argument("--stats_from_frames", action="store_true",
+                        help="compute the Normalize constants from the training frames before training, on the device "
+                             "(geomapnet_amd.pixel_sums; through --device_resize first when that is given), log them, write "
+                             "stats.txt into the log directory and use them; needs --u8_input, excludes --stats_file")
     parser.add_argument("--resident_frames", action="store_true",
                         help="upload the training and validation frames once into one device tensor and gather every batch from "
                              "it by index on the device (geomapnet_amd/resident.py) instead of stacking frames on the host every "
@@ -177,8 +187,18 @@ def run(args, datasets=None, _binding=None, log=print):
                         dropout_active=args.dropout_active, dropout_seed=seed ^ (_rank() << 32), **kw)
     model = posenet if args.model == "posenet" else G.MapNet(mapnet=posenet)
 
+    if args.stats_file is not None and args.stats_from_frames:
+        raise SystemExit("--stats_file and --stats_from_frames exclude each other: one reads the Normalize constants, the other "
+                         "computes them")
+    if (args.stats_file is not None or args.stats_from_frames) and not args.u8_input:
+        raise SystemExit("%s needs --u8_input: the statistics are those of uint8 frames, for the Normalize of the device's input "
+                         "conversion (fp32 frames arrive normalised)" % ("--stats_file" if args.stats_file is not None
+                                                                        else "--stats_from_frames"))
     if args.u8_input:  # the DataLoader ships decoded frames; normalisation happens in the input-conversion kernel
-        model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
+        if args.stats_file is not None:
+            model.set_input_u8(*G.read_stats(args.stats_file))
+        else:  # (--stats_from_frames replaces these once the training frames exist, below)
+            model.set_input_u8(SyntheticFrames.MEAN, SyntheticFrames.STD)
     if args.device_resize is not None:
         if not args.u8_input:
             raise SystemExit("--device_resize needs --u8_input: Resize runs on the device's uint8 frames, before Normalize (fp32 "
@@ -251,6 +271,17 @@ def run(args, datasets=None, _binding=None, log=print):
     if args.learn_gamma:
         experiment_name = "{:s}_learn_gamma".format(experiment_name)
     experiment_name += args.suffix
+    if args.stats_from_frames:  # the statistics of the frames the network will see: after the device's Resize, whole frames
+        sums = G.pixel_sums(train_frames, resize=args.device_resize, **kw)
+        logdir = args.logdir if args.logdir is not None else osp.join(os.getcwd(), "logs", experiment_name)
+        stats_path = osp.join(logdir, "stats.txt")
+        if _rank() == 0:
+            os.makedirs(logdir, exist_ok=True)
+            G.write_stats(stats_path, sums)
+            log("Mean pixel = {}".format(sums.mean()))
+            log("Std. pixel = {}".format(sums.std()))
+            log("{:s} written".format(stats_path))
+        model.set_input_u8(sums.mean(), sums.std())
     trainer = Trainer(model, optimizer, train_criterion, settings, experiment_name, train_set, val_set, device=args.device,
                       checkpoint_file=args.checkpoint, resume_optim=args.resume_optim, val_criterion=val_criterion,
                       logdir=args.logdir, log=log, resident=args.resident_frames)
